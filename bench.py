@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark: images/s of the CGL-GAN worker round (G+D step) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W untimed and K timed rounds, writes the last timed round's outputs when
+--dump-outputs is given, and prints the result line (metric / value / unit / ms_per_step / config / losses).
+--full adds everything that takes runs of its own after the timed region: the in-round per-launch profile
+and the roofline built from it, the CPU-oracle baseline and the 10-round parity leg, at N = 1 the
+"conv_round" and "ring_round" workloads, and --model mdgan's 16-bit "lowp_variant".
 
 Workload (BASELINE.json configs[1] at N=1, configs[2] at N>1):
   * model/mnist_model.py MLP GAN (G 100-128-256-512-1024-784 with BatchNorm1d(eps .8), D 784-512-256-2),
@@ -16,9 +22,14 @@ Workload (BASELINE.json configs[1] at N=1, configs[2] at N>1):
     round all_gather(G losses) -> lambda-weighting -> all_reduce(sum) of the weighted G-output
     gradient -> replicated G update, plus the E-share all_reduce(avg) of D every --E rounds (RCCL).
 A "step" is one round; value = images/s over all ranks = N * 256 * K / max-over-ranks time.
-At N = 1 the line also carries "conv_round": the model/lsgan.py conv GAN round (B=256) timed in its own
-graph-replayed region (--conv-steps rounds, default 60) with its own conv-family roofline -- a second,
+With --full at N = 1 the line also carries "conv_round": the model/lsgan.py conv GAN round (B=256) timed in its
+own graph-replayed region (--conv-steps rounds, default 60) with its own conv-family roofline -- a second,
 labelled workload of the same run, never part of `value`.
+
+--dump-outputs DIR: after the timed rounds, what the last timed round left for its caller is written as
+DIR/<name>.npy (float32, rank 0's worker): the generator output of that round, the updated G / D parameters,
+G's BatchNorm running statistics and the round's losses.  Every input is seeded (dataset, initial weights, the
+on-device z stream and shuffle sampler), so two runs with the same arguments dump the same round.
 """
 import argparse
 import json
@@ -55,10 +66,10 @@ def args_():
                    help="synthetic dataset rows per worker (MNIST train size: 234 full batches + one of 96)")
     p.add_argument("--E", type=int, default=1, help="D-share all-reduce period (N > 1)")
     p.add_argument("--eager", action="store_true", help="launch without hipGraph")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-oracle baseline and parity legs")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--profile-rounds", type=int, default=10,
-                   help="rounds issued launch by launch with per-dispatch events (in-round launch durations)")
+                   help="--full: rounds issued launch by launch with per-dispatch events (in-round launch durations)")
     p.add_argument("--model", choices=["mlp", "lsgan", "mixg", "mdgan", "ring"], default="mlp",
                    help="mlp: model/mnist_model.py CAPGAN round (BASELINE configs[1] at N=1, configs[2] at N>1, "
                         "the default workload); mixg: configs[3], Mix-G through cglgan.driver (num_servers=2 when N "
@@ -67,18 +78,25 @@ def args_():
                         "lsgan: the model/lsgan.py conv GAN round (32x32, MSE/LSGAN loss)")
     p.add_argument("--loss", choices=["mse", "bce"], default="mse", help="conv GAN objective (--model lsgan)")
     p.add_argument("--conv-steps", type=int, default=60,
-                   help="--model mlp at N = 1: also time this many graph-replayed conv GAN rounds (model/lsgan.py, "
+                   help="--full, --model mlp at N = 1: also time this many graph-replayed conv GAN rounds (model/lsgan.py, "
                         "same batch) and report them as 'conv_round' beside the line (0: skip)")
     p.add_argument("--conv-warmup", type=int, default=5)
     p.add_argument("--lowp", choices=["none", "f16", "bf16"], default="f16",
-                   help="--model mdgan: also time the same round with 16-bit GEMM operands (BASELINE configs[4]'s "
+                   help="--full, --model mdgan: also time the same round with 16-bit GEMM operands (BASELINE configs[4]'s "
                         "fp16) and report it beside the fp32 line as 'lowp_variant' (parity unpinned)")
     p.add_argument("--ring-steps", type=int, default=400,
-                   help="--model mlp at N = 1: also time this many graph-replayed CGLGAN 2-D Gaussian-mixture rounds "
+                   help="--full, --model mlp at N = 1: also time this many graph-replayed CGLGAN 2-D Gaussian-mixture rounds "
                         "(configs[0], B=64) and report them as 'ring_round' beside the line (0: skip)")
     p.add_argument("--graph-rounds", type=int, default=int(os.environ.get("CGL_GRAPH_ROUNDS", "10")),
                    help="N = 1 fused rounds: this many complete rounds per hipGraph launch in the timed region "
                         "(cgl_gan_run_graph_rounds; 1 = one graph launch per round)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed rounds also run the in-round launch profile (roofline), the CPU-oracle baseline "
+                        "and parity legs, the 'conv_round' / 'ring_round' workloads (--model mlp at N = 1) and the 16-bit "
+                        "'lowp_variant' (--model mdgan); a plain run times the rounds and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed round left for its caller (generator output, updated G / D "
+                        "parameters, BatchNorm running statistics, losses) as DIR/<name>.npy, float32")
     p.add_argument("--launch-selftest", choices=["ok", "fail"], default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
     if a.batch is None:
@@ -105,6 +123,40 @@ def build_step(a, rank, world):
 def make_exchange(step, world, a):
     from cglgan.exchange import DistComm, WorkerExchange
     return WorkerExchange(step, DistComm() if world > 1 else None, share_every=a.E if world > 1 else 0)
+
+
+DUMP_MAX_ELEMS = 1 << 21    # per array (8 MB of float32); a larger array is dumped as a fixed, seeded sample of this many
+
+
+def dump_outputs(a, rank, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor, the last timed round's results) as DIR/<name>.npy, float32, from
+    rank 0's worker.  An array above DUMP_MAX_ELEMS elements is written as the same seeded sample of its elements
+    (in index order) in every run."""
+    if not a.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(20211212)
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
+def timed_end(a, rank, step):
+    """The end state of the timed rounds of a fused-round model: its stats, and (--dump-outputs) what the last timed
+    round left for the caller of GanStep's round -- the generator output [2B, img] (Xd rows, then Xg rows), the
+    updated flat G / D parameter buffers, G's BatchNorm running statistics and the round's losses
+    [d_loss, d_real, d_fake, g_loss, F, lambda]."""
+    st = step.stats()
+    if a.dump_outputs:
+        losses = torch.tensor([st["d_loss"][0], st["d_real"][0], st["d_fake"][0], st["g_loss"], st["F"], st["lambda"]])
+        dump_outputs(a, rank, {"g_output": step.g_output(), "g_params": step.g_params, "d_params": step.d_params,
+                               "g_running": step.g_running, "losses": losses})
+    return st
 
 
 def profile_inround(step, world, rounds, ex=None):
@@ -382,10 +434,35 @@ def conv_traffic():
             "traffic_algorithmic": p["algorithmic_bytes"], "traffic_ratio": round(p["ratio"], 2)}
 
 
-def conv_round_measure(a, world, rank, steps, warmup, with_cpu):
+def conv_roofline(ops, ms_step):
+    """The conv-family roofline of one round from profile_conv_round's per-op records."""
+    mma_us = sum(o["us"] for o in ops)
+    exe = sum(o["exec_flops"] for o in ops)
+    ref = sum(o["ref_flops"] for o in ops)
+    tf = exe / (mma_us * 1e-6) / 1e12
+    dom = max(ops, key=lambda o: o["us"])
+    return {"bound": "mfma", "kernel": "cgl_conv_fwd + cgl_conv_wgrad (+ pack / reduce), every conv op of "
+                                       "one round", "achieved": round(tf, 3), "peak": PEAK_F32_MFMA,
+            "unit": "TFLOP/s", "frac": round(tf / PEAK_F32_MFMA, 4), **conv_traffic(),
+            "timing": "per conv op: HIP events on the launch stream around the op in one eager round "
+                      "(pack + MFMA kernel, + fixed-order reduction for weight gradients)",
+            "conv_exec_gflop_per_round": round(exe / 1e9, 3),
+            "conv_ref_gflop_per_round": round(ref / 1e9, 3),
+            "conv_us_per_round": round(mma_us, 1),
+            "effective_ref_tflops": round(ref / (mma_us * 1e-6) / 1e12, 3),
+            "step_exec_tflops": round(exe / (ms_step * 1e-3) / 1e12, 3),
+            "dominant_op": {"op": dom["op"], "geom": dom["geom"], "us": round(dom["us"], 1),
+                            "tflops": round(dom["exec_flops"] / (dom["us"] * 1e-6) / 1e12, 2)},
+            "ops": [{"op": o["op"], "geom": o["geom"], "us": round(o["us"], 1),
+                     "tflops": round(o["exec_flops"] / (o["us"] * 1e-6) / 1e12, 2)} for o in ops]}
+
+
+def conv_round_measure(a, world, rank, steps, warmup, with_cpu, dump=False):
     """The model/lsgan.py conv GAN round: W untimed + K timed graph-replayed rounds (barrier + synchronize on
-    both sides, max over ranks), then one eager round with every conv op bracketed by HIP events for the
-    conv-family roofline.  Returns (line, ms_step) on rank 0, (None, ms_step) elsewhere."""
+    both sides, max over ranks), then (--full) one eager round with every conv op bracketed by HIP events for the
+    conv-family roofline.  ``dump``: --dump-outputs applies to this region (the last timed round's generated
+    images Xd / Xg, the updated flat G / D parameter buffers and the losses [d_loss, d_real, d_fake, g_loss, lambda]).
+    Returns (line, ms_step) on rank 0, (None, ms_step) elsewhere."""
     from cglgan.conv_step import ConvGanStep
     from cglgan.exchange import ConvWorkerExchange, DistComm
     stream = torch.cuda.Stream()
@@ -430,17 +507,17 @@ def conv_round_measure(a, world, rank, steps, warmup, with_cpu):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         st = step.stats()
+        if dump and a.dump_outputs:
+            losses = torch.tensor([st["d_loss"], st["d_real"], st["d_fake"], st["g_loss"], st["lambda"]])
+            dump_outputs(a, rank, {"xd": step.xd(), "xg": step.xg(), "g_params": step.G.p, "d_params": step.D.p,
+                                   "losses": losses})
         # per-op timing needs the ops issued one by one: an eager round (same device round state)
-        ops = profile_conv_round(lambda: step.run(eager=True) if world == 1 else ex.round(r, eager=True))
+        ops = (profile_conv_round(lambda: step.run(eager=True) if world == 1 else ex.round(r, eager=True))
+               if a.full else None)
     ms_step = el / steps * 1e3
     value = world * a.batch * steps / el
     if rank != 0:
         return None, ms_step
-    mma_us = sum(o["us"] for o in ops)
-    exe = sum(o["exec_flops"] for o in ops)
-    ref = sum(o["ref_flops"] for o in ops)
-    tf = exe / (mma_us * 1e-6) / 1e12
-    dom = max(ops, key=lambda o: o["us"])
     out = {
         "metric": METRIC + " [conv GAN model/lsgan.py variant]", "value": round(value, 1), "unit": "images/s",
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(ms_step, 4),
@@ -452,39 +529,26 @@ def conv_round_measure(a, world, rank, steps, warmup, with_cpu):
                    "global_batch": a.batch * world, "batch_per_worker": a.batch, "img": "32x32x1",
                    "parallelism": f"workers{world}", "dataset_rows_per_worker": rows,
                    "graph": not a.eager},
-        "roofline": {"bound": "mfma", "kernel": "cgl_conv_fwd + cgl_conv_wgrad (+ pack / reduce), every conv op of "
-                                                "one round", "achieved": round(tf, 3), "peak": PEAK_F32_MFMA,
-                     "unit": "TFLOP/s", "frac": round(tf / PEAK_F32_MFMA, 4), **conv_traffic(),
-                     "timing": "per conv op: HIP events on the launch stream around the op in one eager round "
-                               "(pack + MFMA kernel, + fixed-order reduction for weight gradients)",
-                     "conv_exec_gflop_per_round": round(exe / 1e9, 3),
-                     "conv_ref_gflop_per_round": round(ref / 1e9, 3),
-                     "conv_us_per_round": round(mma_us, 1),
-                     "effective_ref_tflops": round(ref / (mma_us * 1e-6) / 1e12, 3),
-                     "step_exec_tflops": round(exe / (ms_step * 1e-3) / 1e12, 3),
-                     "dominant_op": {"op": dom["op"], "geom": dom["geom"], "us": round(dom["us"], 1),
-                                     "tflops": round(dom["exec_flops"] / (dom["us"] * 1e-6) / 1e12, 2)},
-                     "ops": [{"op": o["op"], "geom": o["geom"], "us": round(o["us"], 1),
-                              "tflops": round(o["exec_flops"] / (o["us"] * 1e-6) / 1e12, 2)} for o in ops]},
+        **({"roofline": conv_roofline(ops, ms_step)} if ops is not None else {}),
         "losses": {"d_loss": st["d_loss"], "g_loss": st["g_loss"], "round": st["round"]},
     }
-    if with_cpu and world == 1 and not a.no_cpu_baseline:
+    if a.full and with_cpu and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_variants(lambda t: conv_cpu_baseline(a, t))
     return out, ms_step
 
 
 def main_lsgan(a, world, rank, local):
-    out, _ = conv_round_measure(a, world, rank, a.steps, a.warmup, with_cpu=True)
+    out, _ = conv_round_measure(a, world, rank, a.steps, a.warmup, with_cpu=True, dump=True)
     if out is not None:
         print(json.dumps(out), flush=True)
     return out
 
 
 def conv_extra(a, world, rank):
-    """The conv GAN round (model/lsgan.py) timed beside the default C2 line at N = 1: its own graph-replayed
+    """--full: the conv GAN round (model/lsgan.py) timed beside the default C2 line at N = 1: its own graph-replayed
     timed region (--conv-steps rounds, default >= 50), its own conv-family roofline, no CPU leg (the conv
-    oracle runs ~300 images/s; `bench.py --model lsgan` reports it).  A labelled extra key, never `value`."""
-    if world != 1 or a.conv_steps <= 0:
+    oracle runs ~300 images/s; `bench.py --model lsgan --full` reports it).  A labelled extra key, never `value`."""
+    if not a.full or world != 1 or a.conv_steps <= 0:
         return None
     out, _ = conv_round_measure(a, world, rank, a.conv_steps, a.conv_warmup, with_cpu=False)
     if out is None:
@@ -638,23 +702,17 @@ def timed_rounds(round_fn, a, world, ex=None):
     return el
 
 
-def fused_report(a, world, rank, step, el, workload, config_extra, cpu_leg=None, parity_kind=None, extra=None,
-                 ex=None, emit=True):
-    """The bench line of a fused-round model (mlp / mixg / mdgan / ring): GEMM-family roofline from the
-    in-round per-launch device durations (profile_inround), CPU baseline and CPU parity at N = 1."""
-    st = step.stats()           # the timed rounds' end state (the profile rounds below advance it)
+def gemm_roofline(a, world, step, ms_step, ex):
+    """--full: the GEMM-family roofline of a fused-round model from the in-round per-launch device durations
+    (profile_inround: --profile-rounds extra rounds after the timed region, which advance the training state)."""
     per_kind, gemm_us, gemm_flops, gemm_n, launches = profile_inround(step, world, a.profile_rounds, ex)
     plan = step.plan_info()
-    ms_step = el / a.steps * 1e3
-    value = world * a.batch * a.steps / el
-    if rank != 0:
-        return None
     # The graph-replayed timed rounds run their launches back to back (the rocprofv3 graph-round timeline,
     # profiles/r04_final_graph_round_timeline.txt: 0.0 us between launches), so the timed period IS the sum of
     # the round's launch durations.  An eager dispatch's event interval differs from the same launch's duration in
     # a graph replay by about the same amount for every launch (rocprofv3 of both: 3.2-3.7 us on each of 27 of
-    # the 28 launches, gpurun_out/r04q), so each launch's duration in the timed rounds = its eager in-round
-    # duration + (timed period - eager sum) / launches: the roofline prices the same rounds `value` counts.
+    # the 28 launches), so each launch's duration in the timed rounds = its eager in-round duration +
+    # (timed period - eager sum) / launches: the roofline prices the same rounds `value` counts.
     # N > 1 (the period also holds the collectives) and --eager keep the eager durations.
     eager_us = sum(v[0] for v in per_kind.values())
     nl = sum(v[1] for v in per_kind.values())
@@ -666,6 +724,48 @@ def fused_report(a, world, rank, step, el, workload, config_extra, cpu_leg=None,
     gemm_raw_tf = gemm_flops / gemm_raw_s / 1e12 if gemm_raw_s > 0 else 0.0
     step_flops = plan["gemm_flops"]
     step_tf = step_flops / (ms_step * 1e-3) / 1e12
+    return {"bound": "mfma", "kernel": "cgl_gemm_f32 (the round's GEMM launches)",
+            "achieved": round(gemm_tf, 3), "peak": PEAK_F32_MFMA, "unit": "TFLOP/s",
+            "frac": round(gemm_tf / PEAK_F32_MFMA, 4),
+            "timing": (f"each launch's in-round device duration (median over {a.profile_rounds} rounds of "
+                       "dispatch begin / end events on the launch stream, cgl_gan_profile) plus the timed "
+                       "graph-replay period's per-launch offset (timed_offset_us = (ms_per_step - eager "
+                       "device sum) / launches)"
+                       if offset != 0.0 else
+                       f"median over {a.profile_rounds} rounds of each launch's in-round device duration "
+                       "(dispatch begin / end events on the launch stream, cgl_gan_profile)"),
+            "timed_offset_us": round(offset, 3),
+            "achieved_eager_raw": round(gemm_raw_tf, 3),
+            "frac_eager_raw": round(gemm_raw_tf / PEAK_F32_MFMA, 4),
+            "eager_raw_note": "GEMM FLOPs / the summed raw in-round eager GEMM durations (no offset model)",
+            "traffic": traffic_per_gemm_launch()[0] if a.model == "mlp" else None,
+            "traffic_unit": "bytes per GEMM launch, all cgl_gemm_f32 instantiations (PMC FETCH_SIZE x2 + WRITE_SIZE)",
+            "traffic_source": traffic_per_gemm_launch()[1] if a.model == "mlp" else None,
+            **(mlp_traffic_algorithmic(a.batch, gemm_n) if a.model == "mlp" else {}),
+            **(traffic_per_launch() if a.model == "mlp" else {}),
+            "gemm_launches_per_round": gemm_n, "gemm_flops_per_round": gemm_flops,
+            "flops_per_gemm_launch": gemm_flops / max(gemm_n, 1),
+            "avg_gemm_launch_us": round(sum(gemm_us) / max(gemm_n, 1) + offset, 3),
+            "avg_gemm_launch_us_eager": round(sum(gemm_us) / max(gemm_n, 1), 3),
+            "gemm_launch_us": [round(u, 2) for u in gemm_us],
+            "step_achieved_tflops": round(step_tf, 3),
+            "step_frac_mfma": round(step_tf / PEAK_F32_MFMA, 4),
+            "per_kind_us_per_round": {k: round(v[0], 2) for k, v in per_kind.items()},
+            "device_us_per_round": round(eager_us, 2),
+            "launches_per_round": plan["launches"], "launches": launches}
+
+
+def fused_report(a, world, rank, step, el, workload, config_extra, cpu_leg=None, parity_kind=None, extra=None,
+                 ex=None, emit=True, st=None):
+    """The bench line of a fused-round model (mlp / mixg / mdgan / ring); with --full also the GEMM-family roofline
+    from the in-round per-launch device durations (gemm_roofline), and at N = 1 the CPU baseline and CPU parity."""
+    if st is None:
+        st = timed_end(a, rank, step)       # the timed rounds' end state (the profile rounds below advance it)
+    ms_step = el / a.steps * 1e3
+    value = world * a.batch * a.steps / el
+    roof = gemm_roofline(a, world, step, ms_step, ex) if a.full else None
+    if rank != 0:
+        return None
     cfg = {"workload": workload, "global_batch": a.batch * world, "batch_per_worker": a.batch,
            "parallelism": f"workers{world}", "graph": not a.eager}
     cfg.update(config_extra)
@@ -675,40 +775,12 @@ def fused_report(a, world, rank, step, el, workload, config_extra, cpu_leg=None,
         "metric": METRIC, "value": round(value, 1), "unit": "images/s", "n_gpus": world, "steps": a.steps,
         "warmup": a.warmup, "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic", "config": cfg,
-        "roofline": {"bound": "mfma", "kernel": "cgl_gemm_f32 (the round's GEMM launches)",
-                     "achieved": round(gemm_tf, 3), "peak": PEAK_F32_MFMA, "unit": "TFLOP/s",
-                     "frac": round(gemm_tf / PEAK_F32_MFMA, 4),
-                     "timing": (f"each launch's in-round device duration (median over {a.profile_rounds} rounds of "
-                                "dispatch begin / end events on the launch stream, cgl_gan_profile) plus the timed "
-                                "graph-replay period's per-launch offset (timed_offset_us = (ms_per_step - eager "
-                                "device sum) / launches)"
-                                if offset != 0.0 else
-                                f"median over {a.profile_rounds} rounds of each launch's in-round device duration "
-                                "(dispatch begin / end events on the launch stream, cgl_gan_profile)"),
-                     "timed_offset_us": round(offset, 3),
-                     "achieved_eager_raw": round(gemm_raw_tf, 3),
-                     "frac_eager_raw": round(gemm_raw_tf / PEAK_F32_MFMA, 4),
-                     "eager_raw_note": "GEMM FLOPs / the summed raw in-round eager GEMM durations (no offset model)",
-                     "traffic": traffic_per_gemm_launch()[0] if a.model == "mlp" else None,
-                     "traffic_unit": "bytes per GEMM launch, all cgl_gemm_f32 instantiations (PMC FETCH_SIZE x2 + WRITE_SIZE)",
-                     "traffic_source": traffic_per_gemm_launch()[1] if a.model == "mlp" else None,
-                     **(mlp_traffic_algorithmic(a.batch, gemm_n) if a.model == "mlp" else {}),
-                     **(traffic_per_launch() if a.model == "mlp" else {}),
-                     "gemm_launches_per_round": gemm_n, "gemm_flops_per_round": gemm_flops,
-                     "flops_per_gemm_launch": gemm_flops / max(gemm_n, 1),
-                     "avg_gemm_launch_us": round(sum(gemm_us) / max(gemm_n, 1) + offset, 3),
-                     "avg_gemm_launch_us_eager": round(sum(gemm_us) / max(gemm_n, 1), 3),
-                     "gemm_launch_us": [round(u, 2) for u in gemm_us],
-                     "step_achieved_tflops": round(step_tf, 3),
-                     "step_frac_mfma": round(step_tf / PEAK_F32_MFMA, 4),
-                     "per_kind_us_per_round": {k: round(v[0], 2) for k, v in per_kind.items()},
-                     "device_us_per_round": round(eager_us, 2),
-                     "launches_per_round": plan["launches"], "launches": launches},
+        **({"roofline": roof} if roof is not None else {}),
         "losses": {"d_loss": st["d_loss"][0], "g_loss": st["g_loss"], "lambda": st["lambda"], "round": st["round"]},
     }
     if extra:
         out.update(extra)
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         if cpu_leg is not None:
             out["cpu_baseline"] = cpu_leg()
         if parity_kind is not None:
@@ -724,6 +796,7 @@ def main_mlp(a, world, rank):
         step, _ = build_step(a, rank, world)
         ex = make_exchange(step, world, a)
         el = timed_rounds(lambda r: ex.round(r, graph=not a.eager), a, world, ex=ex)
+        st = timed_end(a, rank, step)
         conv = conv_extra(a, world, rank)
     ring = ring_extra(a, world, rank)
     extra = {k: v for k, v in (("conv_round", conv), ("ring_round", ring)) if v}
@@ -734,7 +807,7 @@ def main_mlp(a, world, rank):
               f"all-reduce over RCCL")
         return fused_report(a, world, rank, step, el, wl, {"img": "28x28x1", "dataset_rows_per_worker": a.rows},
                             cpu_leg=lambda: cpu_variants(lambda t: cpu_baseline(a, t)), parity_kind="capgan", ex=ex,
-                            extra=extra or None)
+                            extra=extra or None, st=st)
 
 
 def main_driver(a, world, rank, algo):
@@ -750,6 +823,7 @@ def main_driver(a, world, rank, algo):
     with torch.cuda.stream(stream):
         drv = Driver(cfg)
         el = timed_rounds(lambda r: drv.exchange.round(r, graph=cfg.graph), a, world)
+        st = timed_end(a, rank, drv.step)
         if algo == "mixg":
             wl = (f"C4: mixed-gan.py Mix-G, num_workers={world} num_servers={S} (one MixGenerator head per "
                   f"worker, trunk gradient all-reduced in each server group, Cloud trunk FedAvg every round)")
@@ -758,7 +832,7 @@ def main_driver(a, world, rank, algo):
                   + (f", D-swap every {a.E} rounds" if world > 1 else "") + " (fp32 GEMMs; the 16-bit GEMM "
                   "variant is 'lowp_variant')")
         lowp = None
-        if algo == "mdgan" and a.lowp != "none":
+        if a.full and algo == "mdgan" and a.lowp != "none":
             # the same workload with 16-bit GEMM operands (fp32 accumulation, fp32 master weights /
             # BatchNorm / losses / Adam): reported BESIDE the fp32 line, never as its value
             # f16 runs with dynamic loss scaling from torch's default initial scale (GradScaler semantics)
@@ -779,7 +853,7 @@ def main_driver(a, world, rank, algo):
                             {"img": "28x28x1", "num_servers": S, "shard_rows": int(drv.step.real.shape[0])},
                             cpu_leg=lambda: cpu_variants(lambda t: cpu_rounds(algo, a.batch, a.cpu_seconds, t)),
                             parity_kind=algo,
-                            extra={"lowp_variant": lowp} if lowp else None, ex=drv.exchange)
+                            extra={"lowp_variant": lowp} if lowp else None, ex=drv.exchange, st=st)
 
 
 def main_ring(a, world, rank, emit=True):
@@ -808,12 +882,13 @@ def main_ring(a, world, rank, emit=True):
 
 
 def ring_extra(a, world, rank):
-    """BASELINE configs[0] (the CGLGAN/2DMG 2-D Gaussian-mixture round, B=64) timed beside the default C2 line at
-    N = 1: its own graph-replayed timed region (--ring-steps rounds), GEMM-family roofline, 10-round CPU parity and a
-    short CPU-oracle sample.  A labelled extra key, never `value`."""
-    if world != 1 or a.ring_steps <= 0:
+    """--full: BASELINE configs[0] (the CGLGAN/2DMG 2-D Gaussian-mixture round, B=64) timed beside the default C2 line
+    at N = 1: its own graph-replayed timed region (--ring-steps rounds), GEMM-family roofline, 10-round CPU parity and
+    a short CPU-oracle sample.  A labelled extra key, never `value`."""
+    if not a.full or world != 1 or a.ring_steps <= 0:
         return None
     ra = argparse.Namespace(**vars(a))
+    ra.dump_outputs = None               # (--dump-outputs is the headline workload's)
     ra.model, ra.batch, ra.steps, ra.warmup = "ring", default_batch("ring"), a.ring_steps, 20
     ra.cpu_seconds = min(a.cpu_seconds, 3.0)
     out = main_ring(ra, world, rank, emit=False)

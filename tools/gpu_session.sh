@@ -5,9 +5,9 @@
 #   tests        the whole pytest -m gpu suite                      -> gputest.log
 #   tests:FILES  a subset (comma-separated test files)              -> gputest.log
 #   smoke        __graft_entry__.smoke()                            -> smoke.log
-#   bench        bench.py default line (N = 1, with CPU baseline)   -> bench.json
+#   bench        bench.py --full line (N = 1, roofline, conv / ring rounds, CPU baseline) -> bench.json
 #   bench:ARGS   bench.py with ARGS (commas become spaces)          -> bench_<n>.json
-#   lsgan        bench.py --model lsgan --no-cpu-baseline           -> bench_lsgan.json
+#   lsgan        bench.py --model lsgan --full --no-cpu-baseline    -> bench_lsgan.json
 #   prof         rocprofv3 --kernel-trace --stats of a short MLP bench -> prof/ (kernel_stats.csv)
 #   proflsgan    the same for the conv round                        -> prof_lsgan/
 #   traffic      FETCH_SIZE and WRITE_SIZE passes (one counter per run) of the MLP bench -> mlp_FETCH_SIZE/ ...
@@ -40,10 +40,10 @@ for st in "$@"; do
       if [ -n "$arg" ]; then
         timeout -k 10 400 python3 -u bench.py ${arg//,/ } > $O/bench_$n.json 2> $O/bench_$n.err || exit $?
       else
-        timeout -k 10 400 python3 -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
+        timeout -k 10 400 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
       fi ;;
     lsgan)
-      timeout -k 10 400 python3 -u bench.py --model lsgan --no-cpu-baseline > $O/bench_lsgan.json 2> $O/bench_lsgan.err || exit $? ;;
+      timeout -k 10 400 python3 -u bench.py --model lsgan --full --no-cpu-baseline > $O/bench_lsgan.json 2> $O/bench_lsgan.err || exit $? ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
         python3 $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --conv-steps 0 --ring-steps 0 > $O/prof.log 2>&1) || exit $? ;;
