@@ -25,6 +25,7 @@ EXPORTS = [
     "cgl_gan_create", "cgl_gan_destroy", "cgl_gan_reset", "cgl_gan_sync_params", "cgl_gan_sync_params_d", "cgl_gan_gemm_trace", "cgl_gan_run", "cgl_gan_run_graph", "cgl_gan_run_graph_rounds", "cgl_gan_prepare_graph_rounds",
     "cgl_gan_alpha_scale", "cgl_gan_exchange_mode", "cgl_gan_gather_buffers",
     "cgl_gan_exchange_buffer", "cgl_gan_tensor", "cgl_gan_read_stats",
+    "cgl_gan_round_log_capacity", "cgl_gan_read_round_log",
     "cgl_gan_plan_info", "cgl_gan_launch_count", "cgl_gan_launch_info", "cgl_gan_launch_one", "cgl_gan_profile", "cgl_linear_fwd", "cgl_linear_bwd_data", "cgl_linear_bwd_weight", "cgl_adam_step",
     "cgl_normal_fill", "cgl_op_workspace_bytes", "cgl_version", "cgl_act_fwd", "cgl_act_bwd", "cgl_bn1d_fwd",
     "cgl_bn1d_bwd",
@@ -88,6 +89,15 @@ class GanStats(ctypes.Structure):
                 ("loss_scale", ctypes.c_float * 2), ("last_skipped", ctypes.c_int * 2), ("skipped", ctypes.c_int * 2)]
 
 
+class GanRoundRec(ctypes.Structure):
+    """cgl_gan_round_rec: one completed round's scalars in the device round log (192 bytes)."""
+    _fields_ = [("round", ctypes.c_int), ("d_loss", ctypes.c_float * 8), ("d_real", ctypes.c_float * 8),
+                ("d_fake", ctypes.c_float * 8), ("g_loss", ctypes.c_float), ("alpha", ctypes.c_float),
+                ("F", ctypes.c_float), ("lambda_", ctypes.c_float), ("real_rows", ctypes.c_int * 8),
+                ("loss_scale", ctypes.c_float * 2), ("step_skipped", ctypes.c_int * 2),
+                ("reserved_", ctypes.c_int * 7)]
+
+
 def _hip_runtimes():
     """Paths of every libamdhip64 mapped into this process (Linux)."""
     try:
@@ -135,6 +145,8 @@ def _load():
         "cgl_gan_exchange_buffer": (ci, [vp, P(vp), P(i64)]),
         "cgl_gan_tensor": (ci, [vp, ci, P(vp), P(i64)]),
         "cgl_gan_read_stats": (ci, [vp, P(GanStats), vp]),
+        "cgl_gan_round_log_capacity": (ci, []),
+        "cgl_gan_read_round_log": (ci, [vp, ci, ci, P(GanRoundRec), vp]),
         "cgl_gan_plan_info": (ci, [vp, ci, P(ci), P(ci), P(ctypes.c_double)]),
         "cgl_gan_launch_count": (ci, [vp, ci]),
         "cgl_gan_launch_info": (ci, [vp, ci, ci, P(ci), P(cd), P(ci)]),

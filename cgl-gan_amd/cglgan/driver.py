@@ -68,6 +68,26 @@ lr_d = 0.0002
 
 ALGOS = ("capgan", "mixg", "mdgan")
 _DEFAULT_WEIGHTING = {"capgan": "capgan", "mixg": "mix_single", "mdgan": "mean"}
+MAX_ROUNDS_PER_LAUNCH = 64      # CGL_MAX_GRAPH_ROUNDS (include/cglgan.h)
+
+
+def plan_chunks(start: int, n: int, k: int, resume_every: int = 0, log_capacity: int = None):
+    """Cut the ``n`` rounds that follow ``start`` completed ones into launches: chunks of at most ``k`` rounds
+    (and at most ``log_capacity``, so that a whole chunk is still in the round log when it is read), a chunk
+    ending wherever the completed-round count reaches a multiple of ``resume_every`` (the resume file is written
+    between launches).  ``log_every`` does not appear: the per-round lines are read from the device round log
+    after the launch.  Returns the chunk lengths, in order (they sum to ``n``)."""
+    k = max(1, int(k))
+    if log_capacity:
+        k = min(k, int(log_capacity))
+    out, done, end = [], int(start), int(start) + max(0, int(n))
+    while done < end:
+        m = min(k, end - done)
+        if resume_every and resume_every > 0:
+            m = min(m, resume_every - done % resume_every)
+        out.append(m)
+        done += m
+    return out
 
 
 @dataclass
@@ -103,6 +123,9 @@ class DriverConfig:
     graph: bool = True
     gemm_dtype: str = "f32"          # "f16" / "bf16": 16-bit GEMM operands (BASELINE config 5's fp16)
     loss_scale: float = 0.0          # dynamic loss scaling of the 16-bit path (initial scale; 0 = off)
+    rounds_per_launch: int = 10      # rounds per hipGraph launch of a one-worker run (1 .. MAX_ROUNDS_PER_LAUNCH);
+                                     #   the per-round log lines come from the device round log, so log_every does
+                                     #   not shorten the launches.  Does not change the trajectory
 
     @classmethod
     def from_module(cls, **overrides):
@@ -124,6 +147,8 @@ class DriverConfig:
             raise ValueError("iid 2 needs num_class >= num_workers (capgan.py:44)")
         if self.epoch < 1 or self.batch_size < 2:
             raise ValueError("epoch >= 1 and batch_size >= 2 (train-mode BatchNorm)")
+        if not 1 <= self.rounds_per_launch <= MAX_ROUNDS_PER_LAUNCH:
+            raise ValueError(f"rounds_per_launch must be in 1..{MAX_ROUNDS_PER_LAUNCH} (CGL_MAX_GRAPH_ROUNDS)")
         return self
 
     @property
@@ -278,24 +303,70 @@ class Driver:
 
     def run(self, rounds: int = None, log=print):
         """``rounds`` communication rounds (default: num_communication), as Server.run's
-        ``while t > 0`` loop (capgan.py:164-196)."""
+        ``while t > 0`` loop (capgan.py:164-196), issued ``rounds_per_launch`` at a time.  With ``log_every`` a JSON
+        line per due round (``round, server, d_loss, g_loss, lambda, F, s``; ``s`` = host seconds since the call
+        began when the line was emitted) and its lambda appended to ``lambda_list`` (capgan.py:177-183)."""
         cfg = self.cfg
         n = cfg.num_communication if rounds is None else rounds
         if rounds is None:
             n = max(0, n - self.round)          # a resumed run finishes the schedule it started
         t0 = time.perf_counter()
-        for _ in range(n):
-            self.exchange.round(self.round, graph=cfg.graph)
-            self.round += 1
-            if cfg.resume_dir and cfg.resume_every and self.round % cfg.resume_every == 0:
-                self.save_resume()
-            if cfg.log_every and self.round % cfg.log_every == 0:
-                st = self.step.stats()
-                self.lambda_list.append(st.get("lambda"))
-                if self.topo.local == 0 and log is not None:
-                    log(json.dumps({"round": self.round, "server": self.topo.server, "d_loss": st["d_loss"],
-                                    "g_loss": st["g_loss"], "lambda": st.get("lambda"), "F": st.get("F"),
-                                    "s": round(time.perf_counter() - t0, 3)}))
+
+        def emit(r, st):
+            self.lambda_list.append(st.get("lambda"))
+            if self.topo.local == 0 and log is not None:
+                log(json.dumps({"round": r, "server": self.topo.server, "d_loss": st["d_loss"],
+                                "g_loss": st["g_loss"], "lambda": st.get("lambda"), "F": st.get("F"),
+                                "s": round(time.perf_counter() - t0, 3)}))
+
+        if hasattr(self.step, "losses_log"):
+            # Launches of up to rounds_per_launch rounds (one hipGraph each on a one-worker run, round by round
+            # under a group or a Cloud step: WorkerExchange.rounds).  After a launch the records of its rounds due
+            # are read from the device round log with one copy; their lines are formatted and emitted only after
+            # the NEXT launch has been issued, so the GPU works while the host formats and the gap between two
+            # launches is the read alone.  "s" is therefore the host time at which the line was emitted -- up to
+            # one launch after the round's own end.  At a resume point the launch's lines are emitted at once and
+            # the file keeps its place in the sequence: after the lines of the rounds before the one it is written
+            # at, before that round's own line.
+            resume_every = cfg.resume_every if cfg.resume_dir else 0
+            read = getattr(self.step, "read_log", None) or self.step.losses_log
+            to_dicts = getattr(self.step, "log_dicts", None) or (lambda recs: recs)
+            held = None                      # (rounds due, their records) of the launch before the running one
+
+            def lines(h):
+                return list(zip(h[0], to_dicts(h[1])[::cfg.log_every]))
+
+            for m in plan_chunks(self.round, n, cfg.rounds_per_launch, resume_every, self.step.log_capacity):
+                self.exchange.rounds(self.round, m, graph=cfg.graph)
+                if held is not None:
+                    for r, rec in lines(held):
+                        emit(r, rec)
+                    held = None
+                first = self.round + 1
+                self.round += m
+                due = [r for r in range(first, self.round + 1) if cfg.log_every and r % cfg.log_every == 0]
+                if due:
+                    held = (due, read(due[0], due[-1] - due[0] + 1))
+                if resume_every and self.round % resume_every == 0:
+                    ls, held = (lines(held) if held is not None else []), None
+                    last = ls.pop() if ls and ls[-1][0] == self.round else None
+                    for r, rec in ls:
+                        emit(r, rec)
+                    self.save_resume()
+                    if last is not None:
+                        emit(*last)
+            if held is not None:
+                for r, rec in lines(held):
+                    emit(r, rec)
+        else:
+            # a step without a round log (the CPU stand-in of the distributed tests): round by round
+            for _ in range(n):
+                self.exchange.round(self.round, graph=cfg.graph)
+                self.round += 1
+                if cfg.resume_dir and cfg.resume_every and self.round % cfg.resume_every == 0:
+                    self.save_resume()
+                if cfg.log_every and self.round % cfg.log_every == 0:
+                    emit(self.round, self.step.stats())
         if cfg.checkpoint_dir and self.topo.local == 0:
             self.save(cfg.checkpoint_dir)
         if cfg.resume_dir:
@@ -395,6 +466,9 @@ def parse_args(argv=None):
     p.add_argument("--checkpoint_dir", default="")
     p.add_argument("--resume_dir", default="", help="per-worker resume files (written; resumed from if present)")
     p.add_argument("--resume_every", type=int, default=0)
+    p.add_argument("--rounds_per_launch", type=int, default=d.rounds_per_launch,
+                   help=f"rounds per hipGraph launch of a one-worker run (1..{MAX_ROUNDS_PER_LAUNCH}); the per-round "
+                        "log lines are read from the device round log after each launch")
     p.add_argument("--eager", action="store_true", help="launch the round without hipGraph replay")
     p.add_argument("--gemm_dtype", default="f32", choices=["f32", "f16", "bf16"],
                    help="GEMM operand type (f16 / bf16: 16-bit operands, fp32 accumulation; BASELINE config 5)")

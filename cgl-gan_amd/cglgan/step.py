@@ -258,7 +258,10 @@ class GanStep:
         if sd["device_state"].shape != st.shape:
             raise ValueError("resume state: device round state of another build / configuration")
         st.copy_(sd["device_state"])
-        self.sync_params()          # the packed G weights and the next round's z from the loaded state
+        # the loaded state belongs to another timeline: records of the rounds this step ran before must not be
+        # readable under round numbers the resumed run will reach again
+        self.internal(7).zero_()
+        self.sync_params()         # the packed G weights and the next round's z from the loaded state
         torch.cuda.current_stream().synchronize()
 
     # ------------------------------------------------------------------ execution
@@ -293,7 +296,8 @@ class GanStep:
     def run_rounds(self, rounds: int, graph: bool = True):
         """``rounds`` complete rounds (N = 1 or the caller's own lockstep): with ``graph`` one hipGraph launch holding
         them back to back (cgl_gan_run_graph_rounds: no graph-launch boundary between the rounds), else that many
-        ``run()`` calls.  Identical to ``rounds`` calls of ``run(graph=graph)``."""
+        ``run()`` calls.  Identical to ``rounds`` calls of ``run(graph=graph)``.  ``stats()`` afterwards describes
+        the last round; every round of the launch is readable through ``losses_log`` (the device round log)."""
         if rounds <= 0:
             return
         if not graph:
@@ -367,6 +371,50 @@ class GanStep:
                 "d_fake": list(s.d_fake)[:self.epoch], "g_loss": s.g_loss, "alpha": s.alpha, "F": s.F,
                 "lambda": s.lambda_, "bn_batches": s.bn_batches, "loss_scale": list(s.loss_scale),
                 "last_skipped": list(s.last_skipped), "skipped": list(s.skipped)}
+
+    @property
+    def log_capacity(self):
+        """Rounds the device round log keeps (a ring: round r overwrites round r - log_capacity)."""
+        return C.lib.cgl_gan_round_log_capacity()
+
+    def losses_log(self, first: int, count: int):
+        """The scalars of rounds ``first`` .. ``first + count - 1`` (1-based, as ``stats()["round"]`` after each), one
+        dict per round, read from the device round log with one copy (two when the range wraps in the ring) and
+        one stream synchronise -- what the reference prints after every communication round (capgan.py:177-183),
+        also for the rounds inside a ``run_rounds`` launch.  Keys as in ``stats()`` (``round``, ``d_loss``,
+        ``d_real``, ``d_fake``, ``g_loss``, ``alpha``, ``F``, ``lambda``, ``loss_scale``) plus ``real_rows`` (the
+        sampler's rows per local D step) and ``step_skipped`` (``stats()["last_skipped"]`` right after that
+        round).  LookupError when a round of the range is not in the log (not run yet, overwritten, or cleared
+        by ``reset`` / ``load_resume_state``); ValueError for a range no read can take."""
+        return self.log_dicts(self.read_log(first, count))
+
+    def read_log(self, first: int, count: int):
+        """The raw records (``_lib.GanRoundRec`` array, a host copy of its own) of ``losses_log``'s range: the
+        device read without the conversion, for a caller that formats them later (``log_dicts``)."""
+        first, count = int(first), int(count)
+        cap = self.log_capacity
+        if first < 1 or count < 1 or count > cap:
+            raise ValueError(f"rounds {first}..{first + count - 1}: rounds are numbered from 1 and one read takes "
+                             f"1..{cap} of them (the round log's capacity)")
+        if getattr(self, "_log_host", None) is None:     # page-locked: the copy goes straight to it, no staging
+            self._log_host = torch.empty(cap * ctypes.sizeof(C.GanRoundRec), dtype=torch.uint8, pin_memory=True)
+        buf = (C.GanRoundRec * count).from_address(self._log_host.data_ptr())
+        rc = C.lib.cgl_gan_read_round_log(self._h, first, count, buf, _stream())
+        if rc == -2:
+            raise LookupError(f"rounds {first}..{first + count - 1} are not all in the round log (capacity {cap} "
+                              "rounds: not run yet, overwritten, or cleared by reset / a resume load)")
+        C.check(rc, "cgl_gan_read_round_log")
+        out = (C.GanRoundRec * count)()
+        ctypes.memmove(out, buf, ctypes.sizeof(out))
+        return out
+
+    def log_dicts(self, recs):
+        """``read_log``'s records as ``losses_log``'s dicts."""
+        e = self.epoch
+        return [{"round": r.round, "d_loss": list(r.d_loss)[:e], "d_real": list(r.d_real)[:e],
+                 "d_fake": list(r.d_fake)[:e], "g_loss": r.g_loss, "alpha": r.alpha, "F": r.F, "lambda": r.lambda_,
+                 "real_rows": list(r.real_rows)[:e], "loss_scale": list(r.loss_scale),
+                 "step_skipped": list(r.step_skipped)} for r in recs]
 
     def plan_info(self, phase=C.PHASE_ALL):
         nl, ng, fl = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()

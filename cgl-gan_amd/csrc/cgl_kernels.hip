@@ -576,6 +576,9 @@ struct CglAdamArgs {
   long nz;
   unsigned long long zseed;
   int zblk0;
+  // the round log (set on the round's tail launch only, null elsewhere): the thread that runs cgl_round_tail
+  // then writes the completed round's record into slot (round - 1) % CGL_ROUND_LOG_CAP
+  cgl_gan_round_rec* log;
 };
 __device__ __forceinline__ bool cgl_adam_zblock(const CglAdamArgs& a, const CglStepState* st) {
   if (!a.znext || (int)blockIdx.x < a.zblk0) return false;
@@ -651,6 +654,55 @@ __device__ void cgl_round_tail(CglStepState* st) {
   st->round = st->round + 1;   // round complete (read by the next round's prologue)
 }
 
+// The round's end.  `t` is the thread's index counted from the thread that runs the scalar tail (the first thread
+// of the round's last launch's Adam part; its workgroup has 256 threads):
+//   t == 0          the scalar tail, the pending GradScaler update (applied by the next round's prologue), and the
+//                   three words of the round's log record that the tail itself produces (F, lambda, round);
+//   64 <= t < 102   the second wave of that workgroup copies the record's other words, one word per lane.  They
+//                   were all written by earlier launches of the round (losses, alpha, real_rows, scale, found), so
+//                   the copy needs nothing from the tail and runs beside it: the tail thread is the launch's
+//                   longest serial chain, and 38 more loads and stores on it showed in the round time.
+// The record's slot comes from cur_round (the round in progress, written by its prologue) on the copying lanes and
+// from the advanced round counter on the tail thread: the same number.  Plain stores; the host reads the log after
+// a stream synchronise.  loss_scale / step_skipped are what cgl_gan_read_stats reports right after this round.
+#define CGL_ST_W(f) ((int)(offsetof(CglStepState, f) / 4))
+#define CGL_REC_W(f) ((int)(offsetof(cgl_gan_round_rec, f) / 4))
+__device__ __forceinline__ void cgl_round_end(const CglAdamArgs& a, CglStepState* st, long t) {
+  if (t == 0) {
+    cgl_round_tail(st);
+    if (a.scale) st->scaler_pending = 1;   // GradScaler.update runs in the next round's prologue
+    if (a.log) {
+      const int r = st->round;
+      CGL_GLOBAL cgl_gan_round_rec* rec = (CGL_GLOBAL cgl_gan_round_rec*)a.log + ((unsigned)(r - 1) % CGL_ROUND_LOG_CAP);
+      rec->F = st->F;
+      rec->lambda_ = st->lambda;
+      rec->round = r;
+    }
+  } else if (a.log && t >= 64 && t < 64 + 38) {
+    const int w = (int)t - 64;
+    const CGL_GLOBAL unsigned int* s = (const CGL_GLOBAL unsigned int*)st;
+    const unsigned int r = s[CGL_ST_W(cur_round)];
+    CGL_GLOBAL unsigned int* d =
+        (CGL_GLOBAL unsigned int*)((CGL_GLOBAL cgl_gan_round_rec*)a.log + ((r - 1u) % CGL_ROUND_LOG_CAP));
+    if (w < 36) {
+      int so, dw;
+      if (w < 8) so = CGL_ST_W(d_loss) + w, dw = CGL_REC_W(d_loss) + w;
+      else if (w < 16) so = CGL_ST_W(d_loss_parts) + 2 * (w - 8), dw = CGL_REC_W(d_real) + (w - 8);
+      else if (w < 24) so = CGL_ST_W(d_loss_parts) + 2 * (w - 16) + 1, dw = CGL_REC_W(d_fake) + (w - 16);
+      else if (w == 24) so = CGL_ST_W(g_loss_parts), dw = CGL_REC_W(g_loss);
+      else if (w == 25) so = CGL_ST_W(alpha), dw = CGL_REC_W(alpha);
+      else if (w < 34) so = CGL_ST_W(real_rows) + (w - 26), dw = CGL_REC_W(real_rows) + (w - 26);
+      else so = CGL_ST_W(scale) + (w - 34), dw = CGL_REC_W(loss_scale) + (w - 34);
+      d[dw] = s[so];
+    } else {
+      // a.scale set: this round's own found flag (its update is pending); else scaling is off (always 0)
+      const int m = w - 36;
+      d[CGL_REC_W(step_skipped) + m] =
+          a.scale ? (s[CGL_ST_W(found) + m] != 0u ? 1u : 0u) : s[CGL_ST_W(last_skipped) + m];
+    }
+  }
+}
+
 __device__ __forceinline__ void cgl_adam_at(const CglAdamArgs& a, CglStepState* st, int tail, long i) {
   const float ss = a.step_size ? gld(a.step_size) : a.step_size_v;
   const float bc = a.bc2sqrt ? gld(a.bc2sqrt) : a.bc2sqrt_v;
@@ -675,10 +727,7 @@ __device__ __forceinline__ void cgl_adam_at(const CglAdamArgs& a, CglStepState* 
     gst(a.v + i, v);
     gst(a.p + i, p);
   }
-  if (tail && i == 0) {
-    cgl_round_tail(st);
-    if (a.scale) st->scaler_pending = 1;   // GradScaler.update runs in the next round's prologue
-  }
+  if (tail) cgl_round_end(a, st, i);
 }
 
 #ifndef CGL_GEMM_PART_TU   // (the GEMM-instantiation translation units compile only device functions)
@@ -720,10 +769,7 @@ __global__ __launch_bounds__(256) void cgl_adam4(CglAdamArgs a, CglStepState* st
       *(gf4p)(a.p + i4) = p;
     }
   }
-  if (tail && i4 == 0) {
-    cgl_round_tail(st);
-    if (a.scale) st->scaler_pending = 1;
-  }
+  if (tail) cgl_round_end(a, st, i4 >> 2);
 }
 
 // The next round's z from the device round state (cgl_gan_create / _reset / _sync_params): counter st->round + 1,

@@ -307,10 +307,7 @@ __global__ __launch_bounds__(256) void cgl_adam_pack(CglAdamArgs a, CglAdamPack 
       cgl_adam_at(e, st, 0, i);
     }
   }
-  if (tail && b == 0 && threadIdx.x == 0) {   // the round's scalar tail, as cgl_adam_at's thread 0
-    cgl_round_tail(st);
-    if (a.scale) st->scaler_pending = 1;
-  }
+  if (tail && b == 0) cgl_round_end(a, st, threadIdx.x);   // the round's end, as cgl_adam_at's first workgroup
 }
 
 __global__ __launch_bounds__(256) void cgl_round_prologue(CglBeginArgs a, float* z, long nz, unsigned long long zseed,

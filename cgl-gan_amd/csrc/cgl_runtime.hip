@@ -185,8 +185,11 @@ struct WS {
   CglHeadDesc* head;
   CglBnBwdDesc* bnb;
   CglBnApplyDesc* bna;
+  cgl_gan_round_rec* rlog;          // the round log: CGL_ROUND_LOG_CAP records, round r in slot (r - 1) % cap
   int64_t total;
 };
+static_assert(sizeof(cgl_gan_round_rec) % 64 == 0, "round record: whole 64-byte lines");
+static_assert(CGL_ROUND_LOG_CAP >= 4 * CGL_MAX_GRAPH_ROUNDS, "round log: several multi-round launches deep");
 
 WS carve_ws(const cgl_gan_config& c, void* base) {
   WS w;
@@ -244,6 +247,9 @@ WS carve_ws(const cgl_gan_config& c, void* base) {
     if (l >= 1) w.wtpk[l] = cv.take<float>(cgl_pk_floats(g.dims[l], g.dims[l + 1]));
     if (l + 1 < L && g.bn[l]) w.gGpk[l] = cv.take<float>(cgl_pk_floats(B, g.dims[l + 1]));
   }
+  // the round log, after everything else (the layout of the round's own buffers is unchanged).  Not part of
+  // CglStepState: that block is what a resumed run saves as raw words, and its size must not move
+  w.rlog = cv.take<cgl_gan_round_rec>(CGL_ROUND_LOG_CAP);
   w.total = cv.off;
   return w;
 }
@@ -1763,6 +1769,7 @@ int build_plan(cgl_gan* c) {
   param_layout(g, &ng);
   push_adam(c, *ph, c->bufs.g_params, c->bufs.g_grads, c->bufs.g_m, c->bufs.g_v, (long)ng, &st->g_step_size,
             &st->g_bc2sqrt, 1, scaling ? &st->scale[1] : nullptr, scaling ? &st->found[1] : nullptr);
+  ph->back().adam.log = w.rlog;   // the round's tail launch writes the round's record
   if (c->z_ahead) {
     Launch& Ag = ph->back();
     Ag.adam.znext = w.znext;
@@ -2070,6 +2077,7 @@ int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_g
   if (he == hipSuccess) he = hipMemset(c->ws.counters, 0, kCounters * sizeof(unsigned int));
   if (he == hipSuccess) he = hipMemset(c->ws.kcount, 0, kSplitKCounters * sizeof(unsigned int));
   if (he == hipSuccess) he = hipMemset(c->ws.st, 0, sizeof(CglStepState));
+  if (he == hipSuccess) he = hipMemset(c->ws.rlog, 0, CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec));
   if (he == hipSuccess && c->z_ahead) {   // round 1's z
     const long nz = (long)2 * cfg->batch * cfg->g.dims[0];
     hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)((nz / 4 + 255) / 256)), dim3(256), 0, nullptr, c->ws.znext, nz,
@@ -2107,6 +2115,7 @@ int cgl_gan_reset(cgl_gan* c, const float* beta_host, void* stream) {
   HIPCHK(hipMemcpyAsync(c->ws.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(c->ws.counters, 0, kCounters * sizeof(unsigned int), s));
   HIPCHK(hipMemsetAsync(c->ws.kcount, 0, kSplitKCounters * sizeof(unsigned int), s));
+  HIPCHK(hipMemsetAsync(c->ws.rlog, 0, CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec), s));   // a new timeline
   if ((c->pack_adam || c->d_pack) && c->pack_all.blocks > 0) {   // the packed weights from the current parameters
     hipLaunchKernelGGL(cgl_pack_all, dim3(c->pack_all.blocks), dim3(256), 0, s, c->pack_all);
     HIPCHK(hipGetLastError());
@@ -2334,6 +2343,9 @@ int cgl_gan_tensor(cgl_gan* c, int which, float** ptr, int64_t* n) {
   } else if (which == 6) {                          // the device round state (CglStepState, raw words)
     *ptr = (float*)c->ws.st;
     *n = (int64_t)(sizeof(CglStepState) / 4);
+  } else if (which == 7) {                          // the round log (cgl_gan_round_rec ring, raw words)
+    *ptr = (float*)c->ws.rlog;
+    *n = (int64_t)(CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec) / 4);
   } else if (which == 5) {                          // the uploaded GEMM descriptor table (raw words)
     *ptr = (float*)c->ws.gemm;
     *n = (int64_t)(c->gemm.size() * sizeof(CglGemmDesc) / 4);
@@ -2397,6 +2409,25 @@ int cgl_gan_read_stats(cgl_gan* c, cgl_gan_stats* out, void* stream) {
     out->skipped[m] = h.skipped[m] + (h.scaler_pending && h.found[m] != 0u ? 1 : 0);
   }
   return h.err ? CGL_E_STATE : CGL_OK;   // a fused-BatchNorm rendezvous timed out
+}
+
+int cgl_gan_round_log_capacity(void) { return CGL_ROUND_LOG_CAP; }
+
+int cgl_gan_read_round_log(cgl_gan* c, int first_round, int count, cgl_gan_round_rec* out, void* stream) {
+  CGL_BATCH_GUARD();
+  if (!c || !out || first_round < 1 || count < 1 || count > CGL_ROUND_LOG_CAP) return CGL_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  // round r lives in slot (r - 1) % cap: one copy, or two when the range runs past the end of the ring
+  const int slot0 = (int)(((int64_t)first_round - 1) % CGL_ROUND_LOG_CAP);
+  const int n1 = std::min(count, CGL_ROUND_LOG_CAP - slot0);
+  HIPCHK(hipMemcpyAsync(out, c->ws.rlog + slot0, (size_t)n1 * sizeof(cgl_gan_round_rec), hipMemcpyDeviceToHost, s));
+  if (n1 < count)
+    HIPCHK(hipMemcpyAsync(out + n1, c->ws.rlog, (size_t)(count - n1) * sizeof(cgl_gan_round_rec),
+                          hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  for (int i = 0; i < count; ++i)
+    if ((int64_t)out[i].round != (int64_t)first_round + i) return CGL_E_STATE;   // never written / overwritten / cleared
+  return CGL_OK;
 }
 
 int cgl_gan_plan_info(cgl_gan* c, int phase, int* n_launches, int* n_gemm, double* flops) {

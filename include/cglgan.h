@@ -120,6 +120,26 @@ typedef struct cgl_gan_stats {
   int skipped[2];
 } cgl_gan_stats;
 
+/* One completed round's scalars, as the device round log keeps them (cgl_gan_read_round_log): what the
+ * reference prints after every communication round (F and Lambda, capgan.py:177-183) plus the losses behind
+ * them.  The round's last launch (the one that runs the scalar tail; no launch is added) writes record r into
+ * slot (r - 1) % CGL_ROUND_LOG_CAP of a ring in the context workspace, so the rounds of a multi-round graph launch
+ * stay readable one by one.  192 bytes (three 64-byte lines); the layout is part of the ABI. */
+#define CGL_ROUND_LOG_CAP 256
+typedef struct cgl_gan_round_rec {
+  int round;            /* 1-based number of the completed round (0: slot never written / cleared)      */
+  float d_loss[8];      /* as cgl_gan_stats                                                              */
+  float d_real[8], d_fake[8];
+  float g_loss;
+  float alpha;
+  float F;
+  float lambda_;        /* Lambda after the round                                                        */
+  int real_rows[8];     /* real rows of each local D step's batch (device sampler; cgl_gan_tensor 4)     */
+  float loss_scale[2];  /* dynamic loss scaling, 0 = D, 1 = G: the scale this round used ...             */
+  int step_skipped[2];  /* ... and whether its step was skipped (cgl_gan_stats.last_skipped right after) */
+  int reserved_[7];
+} cgl_gan_round_rec;
+
 /* ---------------- layout / sizing queries (host only, no device access) ---------------- */
 /* Number of floats of the flat parameter buffer of G or D (each tensor 256-byte aligned). */
 int64_t cgl_gan_param_count(const cgl_gan_config* cfg, int model);
@@ -166,7 +186,8 @@ int cgl_gan_run_graph(cgl_gan* ctx, int phase, void* stream);
  * cached).  Every round reads its per-round values from the device state the previous one advanced, so this is
  * exactly `rounds` calls of cgl_gan_run_graph(ctx, CGL_PHASE_ALL, stream) without the graph-launch boundary
  * between them (N = 1 worker loops: capgan.py:211-262 + :316-349 repeated over num_communication).  Stats read
- * afterwards describe the last round. */
+ * afterwards describe the last round; every round of the launch left its record in the round log
+ * (cgl_gan_read_round_log). */
 #define CGL_MAX_GRAPH_ROUNDS 64
 int cgl_gan_run_graph_rounds(cgl_gan* ctx, int rounds, void* stream);
 /* Capture and instantiate the `rounds`-round graph (2 <= rounds <= CGL_MAX_GRAPH_ROUNDS) without launching it
@@ -192,6 +213,9 @@ int cgl_gan_exchange_buffer(cgl_gan* ctx, float** ptr, int64_t* n);
  * 3 / 4 = device sampler (sample_n > 0): the round's real-row indices [epoch][batch_real] / real rows
  * of each local D step [epoch] (int32; a pass ends with a short batch of sample_n mod batch_real rows),
  * 5 = the round's GEMM descriptor table as uploaded by cgl_gan_create (raw 32-bit words),
+ * 6 = the device round state (raw 32-bit words; what a resumed run saves and restores),
+ * 7 = the round log, CGL_ROUND_LOG_CAP records of cgl_gan_round_rec as raw 32-bit words (a caller that writes
+ *     the round state from outside -- a resumed run -- zeroes it: the records belong to the old timeline),
  * 16+l / 32+l = gradient w.r.t. layer l's activation / Linear output [B][dims[l+1]] (Xg rows),
  * 48+l / 64+l = layer l's BN+LeakyReLU output / Linear output [2B][dims[l+1]],
  * 80+l / 96+l = saved BN batch mean / invstd [2][dims[l+1]],
@@ -200,6 +224,17 @@ int cgl_gan_exchange_buffer(cgl_gan* ctx, float** ptr, int64_t* n);
 int cgl_gan_tensor(cgl_gan* ctx, int which, float** ptr, int64_t* n);
 /* Synchronous copy of the round scalars to the host. */
 int cgl_gan_read_stats(cgl_gan* ctx, cgl_gan_stats* out, void* stream);
+/* Round log: capacity of the ring in records (host only; CGL_ROUND_LOG_CAP, >= 4 * CGL_MAX_GRAPH_ROUNDS). */
+int cgl_gan_round_log_capacity(void);
+/* Copy the records of rounds first_round ... first_round + count - 1 to the host array `out` (count records): at
+ * most two asynchronous copies on `stream` (two when the range wraps past the end of the ring), then one stream
+ * synchronise.  Every way a round can run writes its record (cgl_gan_run, the captured graphs, the phase A /
+ * phase B halves and the caller's whole-round graphs: all end in the same scalar tail); at n_workers > 1 alpha,
+ * F and lambda_ come from the gathered losses, as in cgl_gan_stats.  cgl_gan_create and cgl_gan_reset clear the
+ * log.  CGL_E_ARG: a null argument, first_round < 1, count < 1 or count > CGL_ROUND_LOG_CAP.  CGL_E_STATE: a
+ * copied record does not hold the round asked for (not run yet, overwritten by round + CGL_ROUND_LOG_CAP, or
+ * cleared); `out` is then unspecified. */
+int cgl_gan_read_round_log(cgl_gan* ctx, int first_round, int count, cgl_gan_round_rec* out, void* stream);
 /* Launch / kernel counts of a phase (for roofline bookkeeping). */
 int cgl_gan_plan_info(cgl_gan* ctx, int phase, int* n_launches, int* n_gemm_launches, double* gemm_flops);
 /* Per-launch access to the plan (instrumented timing: the caller brackets each launch with
