@@ -11,9 +11,9 @@
 #define CGL_IN_PART(p) 1
 #endif
 
-#define CGL_INST_F32(TM, TN, SK, DT, ABN) \
-  CGL_INST_PREFIX __global__ void cgl_gemm_f32<TM, TN, SK, DT, ABN>(const CglGemmDesc* __restrict__, int, int, int, int, \
-                                                                     const int* __restrict__, int);
+#define CGL_INST_F32(TM, TN, DT) \
+  CGL_INST_PREFIX __global__ void cgl_gemm_f32<TM, TN, DT>(const CglGemmDesc* __restrict__, int, int, int, int, \
+                                                           const int* __restrict__, int);
 #define CGL_INST_ARG(TM, TN) \
   CGL_INST_PREFIX __global__ void cgl_gemm_f32_arg<TM, TN>(const CglGemmDesc);
 #define CGL_INST_PRO(TM, TN)                                                                                    \
@@ -25,32 +25,20 @@
                                                         CglStepState*, int);
 
 #if CGL_IN_PART(1)   // the default fp32 plan
-CGL_INST_F32(1, 1, false, CGL_DTYPE_F32, 0)
-CGL_INST_F32(2, 2, false, CGL_DTYPE_F32, 0)
+CGL_INST_F32(1, 1, CGL_DTYPE_F32)
+CGL_INST_F32(2, 2, CGL_DTYPE_F32)
 CGL_INST_PRO(1, 1)
 CGL_INST_PRO(2, 2)
 #endif
-#if CGL_IN_PART(2)   // fp32 split-K, the forward BatchNorm operand transform, the single-op (by-value) form
+#if CGL_IN_PART(2)   // the single-op (by-value) form, f16 operands
 CGL_INST_ARG(1, 1)
 CGL_INST_ARG(2, 2)
-CGL_INST_F32(1, 1, true, CGL_DTYPE_F32, 0)
-CGL_INST_F32(2, 2, true, CGL_DTYPE_F32, 0)
-CGL_INST_F32(1, 1, false, CGL_DTYPE_F32, 1)
-CGL_INST_F32(2, 2, false, CGL_DTYPE_F32, 1)
+CGL_INST_F32(1, 1, CGL_DTYPE_F16)
+CGL_INST_F32(2, 2, CGL_DTYPE_F16)
 #endif
-#if CGL_IN_PART(3)   // the backward BatchNorm operand transform, f16 operands
-CGL_INST_F32(1, 1, false, CGL_DTYPE_F32, 2)
-CGL_INST_F32(2, 2, false, CGL_DTYPE_F32, 2)
-CGL_INST_F32(1, 1, true, CGL_DTYPE_F16, 0)
-CGL_INST_F32(2, 2, true, CGL_DTYPE_F16, 0)
-CGL_INST_F32(1, 1, false, CGL_DTYPE_F16, 0)
-CGL_INST_F32(2, 2, false, CGL_DTYPE_F16, 0)
-#endif
-#if CGL_IN_PART(4)   // bf16 operands, the weight-gradient + Adam fusion
-CGL_INST_F32(1, 1, true, CGL_DTYPE_BF16, 0)
-CGL_INST_F32(2, 2, true, CGL_DTYPE_BF16, 0)
-CGL_INST_F32(1, 1, false, CGL_DTYPE_BF16, 0)
-CGL_INST_F32(2, 2, false, CGL_DTYPE_BF16, 0)
+#if CGL_IN_PART(3)   // bf16 operands, the weight-gradient + Adam fusion
+CGL_INST_F32(1, 1, CGL_DTYPE_BF16)
+CGL_INST_F32(2, 2, CGL_DTYPE_BF16)
 CGL_INST_ADAM(1, 1)
 CGL_INST_ADAM(2, 2)
 #endif

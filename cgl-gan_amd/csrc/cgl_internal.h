@@ -10,7 +10,6 @@
 #define CGL_WAVE 64
 #define CGL_GEMM_THREADS 256
 #define CGL_GEMM_KCHUNK 16           // k per MFMA chunk: 8 per lane half (k-permuted)
-#define CGL_BN_MAXF 1024             // max features of a G BatchNorm layer
 
 enum { CGL_EPI_ACT_NONE = 0, CGL_EPI_ACT_LEAKY = 1, CGL_EPI_ACT_TANH = 2, CGL_EPI_ACT_SIGMOID = 3 };
 
@@ -102,25 +101,11 @@ struct CglBnFwd {
   float* save_invstd;
 };
 
-// Backward BatchNorm1d of a GEMM's A operand (a_bn 2): the A values are dy (LeakyReLU'-masked
-// gradient w.r.t. the BatchNorm output) stored by the previous GEMM together with per-row-tile
-// partials {sum dy, sum (y - mean) dy}; dZ = (dy - S/M - (y - mean) D invstd^2 / M) invstd gamma.
-#define CGL_BNB_TAB (CGL_BN_MAXF + 16)   // LDS table stride (floats; padding for the K-tail chunk)
-struct CglBnBwdFold {
-  const double* part;     // [tiles][F][2]
-  int tiles, F, M;        // producer row tiles, features, rows of the BatchNorm call
-  const float* mean; const float* invstd; const float* gamma;   // [F] (the call's saved statistics)
-  float* g_gamma; float* g_beta;       // written by workgroup 0 of the k-contiguous problem
-  const float* y; int ldy;             // BatchNorm input rows (same row / column positions as A)
-};
-
 struct CglGemmDesc {
   int M, N, K;
   int WM, WN, WK;         // wave arrangement, WM*WN*WK == 4
   int tiles_m, tiles_n;
   int wg_begin;           // first workgroup of this problem in a grouped launch
-  int xcd_pm;             // XCD blocking: the tile grid is cut into xcd_pm x (8 / xcd_pm) slabs, slab x on XCD x
-                          // (its L2 then holds 1 / xcd_pm of A and xcd_pm / 8 of B); 0 = n-major ranges
   int layout;             // 0: NT (A[m][k], B[n][k]); 1: NN (A[m][k], B[k][n]); 2: TN (A[k][m], B[k][n])
   int a_vec, b_vec;       // 16-byte vector loads allowed along each operand's contiguous dim
   int TM, TN;             // 32x32 accumulator blocks per wave (1x1 or 2x2)
@@ -143,23 +128,6 @@ struct CglGemmDesc {
   // row ((r & (2^lp - 1)) << lq) + (r >> lp) of C (and of bias_out) -- the NHWC -> NCHW feature order of a weight
   // gradient whose A operand is an NHWC activation gradient (cgl_linear_prepare_wgrad_nhwc); plain stores only
   int c_perm;
-  // cross-workgroup split-K (ksplit > 1): the K range is cut into ksplit slices, one workgroup per
-  // (tile, slice); every slice stores its tile partial write-through (sc1) to kpart, the workgroup
-  // that draws the last ticket of kcount[tile] sums the partials in slice order (deterministic),
-  // runs the epilogue and re-zeroes the ticket
-  int ksplit;
-  float* kpart;                        // [ksplit][tiles][WM*WN][TM*TN][16][64] floats
-  unsigned int* kcount;                // [tiles], zero at rest
-  // A-operand transform (cgl_gemm.hip): 0 none, 1 forward BatchNorm1d + LeakyReLU (a_bnf),
-  // 2 backward BatchNorm1d (a_bnb); its LDS tables take the first tab_floats of the dynamic LDS
-  int a_bn;
-  int tab_floats;
-  CglBnFwd a_bnf;
-  CglBnBwdFold a_bnb;
-  // backward BatchNorm partials of the stored output dy: [tiles_m][N][2] {sum dy, sum (y - mean) dy}
-  double* bnb_part;
-  const float* bnb_y; int bnb_ld;      // the BatchNorm input at the stored positions
-  const float* bnb_mean;               // its saved batch mean [N]
   // dynamic loss scaling (16-bit instantiations only): a stored non-finite value raises *inf_flag
   unsigned int* inf_flag;
   // epilogue Adam (the ADAM instantiation: G's first-layer weight gradient fused with the G Adam launch):
@@ -230,7 +198,6 @@ struct CglHeadDesc {
   const float* scale_dev; // dynamic loss scaling: the dlogits (and dP) carry this factor, the loss does not
   float combine;          // D_loss = (seg0 + seg1) * combine  (0.5: capgan.py:339, 1: CGLGAN/2DMG/main.py:364)
   float* combine_out;     // optional
-  const float* combine_in0;  // segment-0 mean computed by another launch (when this one has no segment 0)
   int rows_per_wg;
   int deferred;           // the batch-mean reduction is left to the next GEMM launch's finisher workgroup
   int nwg;                // (deferred) this launch's workgroups = partials to reduce

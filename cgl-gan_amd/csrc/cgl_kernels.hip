@@ -42,7 +42,7 @@ __device__ void cgl_head_finish(const CglHeadDesc* __restrict__ hd, int nwg, flo
     }
     const int n0s = min(hd->split, M), n1 = M - n0s;
     const int n0 = hd->n0_dev ? min(gldi(hd->n0_dev), n0s) : n0s;
-    const float l0 = n0 > 0 ? (float)(s0 / n0) : (hd->combine_in0 ? gld(hd->combine_in0) : 0.f);
+    const float l0 = n0 > 0 ? (float)(s0 / n0) : 0.f;
     const float l1 = n1 > 0 ? (float)(s1 / n1) : 0.f;
     if (hd->loss_out0 && n0 > 0) gst(hd->loss_out0, l0);
     if (hd->loss_out2 && n0 > 0) gst(hd->loss_out2, l0);
@@ -192,7 +192,74 @@ __device__ __forceinline__ void cgl_head_loss_body(const CglHeadDesc* __restrict
 }
 #endif   // CGL_GEMM_PART_TU
 
-// (cgl_bn_stats: cgl_gemm.hip, shared with the GEMMs that fold the BatchNorm into their loads)
+// BatchNorm statistics of group g for Q features k[q] (k[q] < 0: unused) from the producer
+// partials: the exact parallel combination of per-tile {S_t, M2_t} over c_t rows, in double
+// like torch's CPU kernel and in a fixed tile order,
+//   mean = sum_t S_t / n,   M2 = sum_t (M2_t + c_t (S_t / c_t - mean)^2).
+// Fast path (<= 8 tiles per group): every {S_t, M2_t} pair of the Q features is loaded up front
+// as one 8-byte load, so the whole computation costs a single memory round trip.
+template <int Q>
+__device__ __forceinline__ void cgl_bn_stats(const CglBnFwd& bn, int K, const int (&k)[Q], int g, double (&mean)[Q],
+                                             double (&m2)[Q], int& n) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const int r0 = g * bn.gr, r1 = min(r0 + bn.gr, bn.mtot);
+  n = r1 - r0;
+  const int t0 = r0 / bn.part_bm, t1 = (r1 - 1) / bn.part_bm;
+  const int nt = t1 - t0 + 1;
+  if (nt <= 8) {
+    f32x2 pr[Q][8];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int kk = max(k[q], 0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int t = t0 + min(j, nt - 1);
+        const int slot = (t * bn.part_bm < r0) ? 1 : 0;   // tile starts in the previous group
+        pr[q][j] = *(const CGL_GLOBAL f32x2*)(bn.part + ((long)(t * 2 + slot) * K + kk) * 2);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < nt) s += (double)pr[q][j][0];
+      const double mu = s / n;
+      double acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (j < nt) {
+          const int t = t0 + j;
+          const int c = min((t + 1) * bn.part_bm, r1) - max(t * bn.part_bm, r0);
+          const double dd = (double)pr[q][j][0] / c - mu;
+          acc += (double)pr[q][j][1] + c * dd * dd;
+        }
+      }
+      mean[q] = mu;
+      m2[q] = acc;
+    }
+    return;
+  }
+  for (int q = 0; q < Q; ++q) {
+    const int kk = max(k[q], 0);
+    double s = 0.0;
+    for (int t = t0; t <= t1; ++t) {
+      const int slot = (t * bn.part_bm < r0) ? 1 : 0;
+      s += (double)gld(bn.part + ((long)(t * 2 + slot) * K + kk) * 2);
+    }
+    const double mu = s / n;
+    double acc = 0.0;
+    for (int t = t0; t <= t1; ++t) {
+      const int slot = (t * bn.part_bm < r0) ? 1 : 0;
+      const float* pp = bn.part + ((long)(t * 2 + slot) * K + kk) * 2;
+      const int c = min((t + 1) * bn.part_bm, r1) - max(t * bn.part_bm, r0);
+      const double dd = (double)gld(pp) / c - mu;
+      acc += (double)gld(pp + 1) + c * dd * dd;
+    }
+    mean[q] = mu;
+    m2[q] = acc;
+  }
+}
 
 // BatchNorm1d(train) + LeakyReLU of one G layer's [mtot][F] output, torch's arithmetic:
 //   invstd = 1 / sqrt(var_biased + eps),  scale = invstd * gamma,  shift = beta - mean * scale,
@@ -286,7 +353,7 @@ __device__ __forceinline__ void cgl_bnb_store_gb(const CglBnBwdDesc* __restrict_
   gst(bd->g_beta + f, db);
   if (bd->inf_flag && !(isfinite(dg) && isfinite(db))) atomicOr(bd->inf_flag, 1u);
 }
-// FPW features per workgroup (32: the original layout; 16 / 8 / 4 give 2x / 4x / 8x the workgroups for the narrow
+// FPW features per workgroup (32: the single-op form; 8, the round's, gives 4x the workgroups for the narrow
 // layers, each thread then owning fewer rows): NRG = 256 / FPW row groups, rows of a group in registers.
 template <int FPW>
 __device__ __forceinline__ void cgl_bn_bwd_body(const CglBnBwdDesc* __restrict__ bd) {
@@ -424,10 +491,7 @@ __global__ __launch_bounds__(256) void cgl_head_loss(const CglHeadDesc d) {
 __global__ __launch_bounds__(256) void cgl_bn_apply(const CglBnApplyDesc d) {
   cgl_bn_apply_body(&d, blockIdx.x, blockIdx.y);
 }
-__global__ __launch_bounds__(256) void cgl_bn_bwd(const CglBnBwdDesc d) { cgl_bn_bwd_body<32>(&d); }
-__global__ __launch_bounds__(256) void cgl_bn_bwd16(const CglBnBwdDesc d) { cgl_bn_bwd_body<16>(&d); }
 __global__ __launch_bounds__(256) void cgl_bn_bwd8(const CglBnBwdDesc d) { cgl_bn_bwd_body<8>(&d); }
-__global__ __launch_bounds__(256) void cgl_bn_bwd4(const CglBnBwdDesc d) { cgl_bn_bwd_body<4>(&d); }
 // the single-op entry point (cgl_bn1d_bwd): the descriptor travels in the kernel arguments
 __global__ __launch_bounds__(256) void cgl_bn_bwd_arg(const CglBnBwdDesc d) { cgl_bn_bwd_body<32>(&d); }
 #endif   // CGL_GEMM_PART_TU
@@ -790,7 +854,6 @@ __global__ __launch_bounds__(CGL_GEMM_THREADS) void cgl_gemm_adam(const CglGemmD
                                                                  int gemm_wgs, CglAdamArgs comp, CglStepState* st,
                                                                  int tail) {
   extern __shared__ float cgl_dyn_lds[];
-  __shared__ int s_flag[1];
   __shared__ double s_bnd[4 * TN * 32 * 2];
   const int bid = blockIdx.x;
   if (bid >= gemm_wgs) {
@@ -803,9 +866,9 @@ __global__ __launch_bounds__(CGL_GEMM_THREADS) void cgl_gemm_adam(const CglGemmD
   const CglGemmDesc* __restrict__ d = descs + di;
   if (d->layout != 2) return;     // planner: the fused weight gradient is a TN problem
   if (d->a_vec && d->b_vec)
-    cgl_gemm_body<2, 1, TM, TN, false, CGL_DTYPE_F32, 0, true>(d, bid, cgl_dyn_lds, s_flag, s_bnd);
+    cgl_gemm_body<2, 1, TM, TN, CGL_DTYPE_F32, true>(d, bid, cgl_dyn_lds, s_bnd);
   else
-    cgl_gemm_body<2, 0, TM, TN, false, CGL_DTYPE_F32, 0, true>(d, bid, cgl_dyn_lds, s_flag, s_bnd);
+    cgl_gemm_body<2, 0, TM, TN, CGL_DTYPE_F32, true>(d, bid, cgl_dyn_lds, s_bnd);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -328,7 +328,6 @@ __global__ __launch_bounds__(CGL_GEMM_THREADS) void cgl_gemm_pro(const CglGemmDe
                                                                 unsigned long long zseed, int* idx, int epoch, int br,
                                                                 int n, unsigned long long sseed, CglOpPack pk) {
   extern __shared__ float cgl_dyn_lds[];
-  __shared__ int s_flag[1];
   __shared__ double s_bnd[4 * TN * 32 * 2];
   const int bid = blockIdx.x;
   if (bid >= gemm_wgs) {
@@ -340,8 +339,8 @@ __global__ __launch_bounds__(CGL_GEMM_THREADS) void cgl_gemm_pro(const CglGemmDe
   const CglGemmDesc* __restrict__ d = descs;
   if (d->layout != 0) return;     // planner: an NT problem (A = z rows)
   if (d->a_vec && d->b_vec)
-    cgl_gemm_body<0, 1, TM, TN, false, CGL_DTYPE_F32, 0>(d, bid, cgl_dyn_lds, s_flag, s_bnd);
+    cgl_gemm_body<0, 1, TM, TN>(d, bid, cgl_dyn_lds, s_bnd);
   else
-    cgl_gemm_body<0, 0, TM, TN, false, CGL_DTYPE_F32, 0>(d, bid, cgl_dyn_lds, s_flag, s_bnd);
+    cgl_gemm_body<0, 0, TM, TN>(d, bid, cgl_dyn_lds, s_bnd);
   asm volatile("" ::"v"(pfv));
 }

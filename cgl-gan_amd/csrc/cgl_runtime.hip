@@ -131,9 +131,7 @@ constexpr int kMaxGemmDescs = 128;
 constexpr int64_t kTraceWords = CGL_GEMM_TRACE_W * CGL_GEMM_TRACE_WGS;   // CGL_GEMM_TRACE stamps
 constexpr int kMaxHeadDescs = 2 * CGL_MAX_EPOCH + 4;
 constexpr int kMaxBnDescs = 2 * CGL_MAX_LAYERS;
-constexpr int kSplitKCounters = 8192;           // split-K tickets (one per tile of a launch)
 constexpr int kCounters = 64;                    // head-loss tickets
-constexpr int64_t kSplitKFloats = 4 << 20;       // split-K partials of one launch (16 MiB)
 
 // An exchange buffer (dYL, or a Mix-G trunk gradient gdA / gG) is followed by kXchgPad floats: the gathered
 // exchange (cgl_gan_exchange_mode 1) sends [gradient | G loss | padding] as one slot of xchg_slot(n) floats.
@@ -167,11 +165,7 @@ struct WS {
   float* gG[CGL_MAX_LAYERS];
   // misc
   float* hpart;
-  float* hpart2;
   unsigned int* counters;   // [kCounters]: head-loss tickets
-  float* kpart;             // [kSplitKFloats]: split-K partials (reused by every launch)
-  unsigned int* kcount;     // [kSplitKCounters]: split-K tickets (zero at rest)
-  double* gdpart[CGL_MAX_LAYERS];   // backward BatchNorm partials of dy [B/32][f][2] (a_bn 2)
   float* gpk[CGL_MAX_LAYERS];       // packed BatchNorm + LeakyReLU output P(act_l; 2B, f) (next GEMM's A)
   float* wpk[CGL_MAX_LAYERS];       // packed G weights P(W_l; fo, fi) (the forward GEMM's B)
   float* wtpk[CGL_MAX_LAYERS];      // packed transposed G weights P(W_l^T; fi, fo) (input-gradient B)
@@ -228,7 +222,6 @@ WS carve_ws(const cgl_gan_config& c, void* base) {
   w.dlog = cv.take<float>((int64_t)Md * d.dims[J]);
   w.dYL = cv.take<float>((int64_t)B * g.dims[L] + kXchgPad);
   w.hpart = cv.take<float>((int64_t)((Md + kHeadRows - 1) / kHeadRows) * 2);
-  w.hpart2 = cv.take<float>((int64_t)((Md + kHeadRows - 1) / kHeadRows) * 2);
   w.idx = cv.take<int>((int64_t)c.epoch * c.batch_real);
   w.znext = cv.take<float>((int64_t)2 * B * g.dims[0]);
   w.gath = cv.take<float>((int64_t)std::max(c.n_workers, 1) * xchg_slot_max(c));
@@ -236,11 +229,6 @@ WS carve_ws(const cgl_gan_config& c, void* base) {
     w.dwpk[j] = cv.take<float>(cgl_pk_floats(d.dims[j + 1], d.dims[j]));
     w.dwtpk[j] = cv.take<float>(cgl_pk_floats(d.dims[j], d.dims[j + 1]));
   }
-  // split-K scratch last, so that the layout of everything the default plan touches is unchanged
-  w.kpart = cv.take<float>(kSplitKFloats);
-  w.kcount = cv.take<unsigned int>(kSplitKCounters);
-  for (int l = 0; l + 1 < L; ++l)
-    if (g.bn[l]) w.gdpart[l] = cv.take<double>((int64_t)((B + 31) / 32) * g.dims[l + 1] * 2);
   for (int l = 0; l < L; ++l) {
     if (l + 1 < L && g.bn[l]) w.gpk[l] = cv.take<float>(cgl_pk_floats(2 * B, g.dims[l + 1]));
     w.wpk[l] = cv.take<float>(cgl_pk_floats(g.dims[l + 1], g.dims[l]));
@@ -270,14 +258,9 @@ struct Launch {
   int nb_norm = 0, nb_samp = 0;
   int stream_id = 0;
   double flops = 0.0;
-  int stream = 0;       // 0: the caller's stream, 1: the context's side stream
-  int wait_ev = -1;     // event waited on before the launch / recorded after it
-  int record_ev = -1;
   int shmem = 0;        // dynamic LDS bytes (GEMM)
   int blk = 1;          // GEMM per-wave block shape (TM = TN = blk)
-  bool sk = false;      // GEMM launch holds a split-K problem
   int dt = CGL_DTYPE_F32;   // GEMM operand type (cgl_gan_config.gemm_dtype)
-  int abn = 0;              // GEMM operand-transform instantiation (the launch's a_bn)
   bool adpk = false;        // K_ADAM: the cgl_adam_pack form (cgl_gan.adam_pack, or adam_pack_d for D's Adam)
   int apk_d = 0;            // K_ADAM adpk: 1 = D's (cgl_gan.adam_pack_d)
   bool v4 = false;          // K_ADAM (not adpk): the four-elements-per-thread form (cgl_adam4)
@@ -300,17 +283,12 @@ void klaunch(void (*k)(KArgs...), dim3 grid, dim3 block, uint32_t shmem, hipStre
     hipLaunchKernelGGL(k, grid, block, shmem, s, ((KArgs)args)...);
 }
 
-// Split-K partials of 2x2-block waves need up to 48 KB of dynamic LDS (+ the 20 KB operand tables).
+// Split-K partials of 2x2-block waves need up to 48 KB of dynamic LDS.
 hipError_t gemm_lds_attr() {
   static bool done = false;
   if (!done) {
     // advisory on this platform (launches up to the per-CU LDS succeed); never fail on it
-    for (const void* fn : {(const void*)cgl_gemm_f32<1, 1>, (const void*)cgl_gemm_f32<2, 2>,
-                           (const void*)cgl_gemm_f32<1, 1, true>, (const void*)cgl_gemm_f32<2, 2, true>,
-                           (const void*)cgl_gemm_f32<1, 1, false, CGL_DTYPE_F32, 1>,
-                           (const void*)cgl_gemm_f32<2, 2, false, CGL_DTYPE_F32, 1>,
-                           (const void*)cgl_gemm_f32<1, 1, false, CGL_DTYPE_F32, 2>,
-                           (const void*)cgl_gemm_f32<2, 2, false, CGL_DTYPE_F32, 2>}) {
+    for (const void* fn : {(const void*)cgl_gemm_f32<1, 1>, (const void*)cgl_gemm_f32<2, 2>}) {
       for (int kb : {150, 128, 96, 64}) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kb * 1024);
         (void)hipGetLastError();
@@ -320,20 +298,6 @@ hipError_t gemm_lds_attr() {
     done = true;
   }
   return hipSuccess;
-}
-
-template <int DT>
-void launch_gemm16(int blk, int grid, int shmem, hipStream_t s, const CglGemmDesc* d, CglGemmSel n, bool sk) {
-  if (sk) {
-    if (blk == 2)
-      klaunch(cgl_gemm_f32<2, 2, true, DT>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-    else
-      klaunch(cgl_gemm_f32<1, 1, true, DT>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-  } else if (blk == 2) {
-    klaunch(cgl_gemm_f32<2, 2, false, DT>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-  } else {
-    klaunch(cgl_gemm_f32<1, 1, false, DT>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-  }
 }
 
 // The problem selection of a launch (CglGemmSel) from the host copies of its n problems.
@@ -348,32 +312,21 @@ CglGemmSel gemm_sel(const CglGemmDesc* hd, int n) {
 }
 
 // d: the device descriptors of the launch, n: their selection (gemm_sel of the host copies)
-void launch_gemm(int blk, int grid, int shmem, hipStream_t s, const CglGemmDesc* d, CglGemmSel n, bool sk = false,
-                 int dt = CGL_DTYPE_F32, int abn = 0) {
-  if (abn == 1) {          // fp32, no split-K (planner)
-    if (blk == 2)
-      klaunch(cgl_gemm_f32<2, 2, false, CGL_DTYPE_F32, 1>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-    else
-      klaunch(cgl_gemm_f32<1, 1, false, CGL_DTYPE_F32, 1>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-  } else if (abn == 2) {
-    if (blk == 2)
-      klaunch(cgl_gemm_f32<2, 2, false, CGL_DTYPE_F32, 2>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-    else
-      klaunch(cgl_gemm_f32<1, 1, false, CGL_DTYPE_F32, 2>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-  } else if (dt == CGL_DTYPE_F16) {
-    launch_gemm16<CGL_DTYPE_F16>(blk, grid, shmem, s, d, n, sk);
-  } else if (dt == CGL_DTYPE_BF16) {
-    launch_gemm16<CGL_DTYPE_BF16>(blk, grid, shmem, s, d, n, sk);
-  } else if (sk) {   // a launch with a split-K problem: the instantiation carrying the combine
-    if (blk == 2)
-      klaunch(cgl_gemm_f32<2, 2, true>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-    else
-      klaunch(cgl_gemm_f32<1, 1, true>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-  } else if (blk == 2) {
-    klaunch(cgl_gemm_f32<2, 2>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-  } else {
-    klaunch(cgl_gemm_f32<1, 1>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
-  }
+template <int DT>
+void launch_gemm_dt(int blk, int grid, int shmem, hipStream_t s, const CglGemmDesc* d, CglGemmSel n) {
+  if (blk == 2)
+    klaunch(cgl_gemm_f32<2, 2, DT>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
+  else
+    klaunch(cgl_gemm_f32<1, 1, DT>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, n.wg1, n.wg2, n.meta, n.fin, n.pf, n.pf_lines);
+}
+void launch_gemm(int blk, int grid, int shmem, hipStream_t s, const CglGemmDesc* d, CglGemmSel n,
+                 int dt = CGL_DTYPE_F32) {
+  if (dt == CGL_DTYPE_F16)
+    launch_gemm_dt<CGL_DTYPE_F16>(blk, grid, shmem, s, d, n);
+  else if (dt == CGL_DTYPE_BF16)
+    launch_gemm_dt<CGL_DTYPE_BF16>(blk, grid, shmem, s, d, n);
+  else
+    launch_gemm_dt<CGL_DTYPE_F32>(blk, grid, shmem, s, d, n);
 }
 
 // Cost model of one GEMM launch (cycles) used to pick the wave arrangement WM x WN x WK and
@@ -381,92 +334,30 @@ void launch_gemm(int blk, int grid, int shmem, hipStream_t s, const CglGemmDesc*
 //   MFMA issue per SIMD, one wave's dependent chain incl. the part of the memory latency its
 //   (S-1)-deep prefetch does not cover, and the per-CU address/L1 rate of the fragment loads
 //   (a fragment load touches 32 cache lines), plus the split-K reduction.
-//   KS > 1: cross-workgroup split-K -- KS times the workgroups, 1 / KS of the chunks each, plus
-//   the combine (publish, ticket, the reducer's read of KS partials).
-double gemm_cost(int M, int N, int K, int WM, int WN, int WK, int TM, int TN, int KS = 1, double ta_a = 1.0,
-                 double ta_b = 1.0) {
+double gemm_cost(int M, int N, int K, int WM, int WN, int WK, int TM, int TN, double ta_a = 1.0, double ta_b = 1.0) {
   const double lat = 2000.0;
   const int S = 3;
   const long tiles = (long)((M + 32 * TM * WM - 1) / (32 * TM * WM)) * ((N + 32 * TN * WN - 1) / (32 * TN * WN));
-  const double wg_per_cu = std::ceil(tiles * KS / 256.0);
+  const double wg_per_cu = std::ceil(tiles / 256.0);
   const int nch = (K + CGL_GEMM_KCHUNK - 1) / CGL_GEMM_KCHUNK;
-  const double per = std::ceil((double)nch / (WK * KS));
+  const double per = std::ceil((double)nch / WK);
   const double blk = 512.0 * TM * TN;
   const double mfma = wg_per_cu * per * blk;
   const double chain = per * std::max(blk, lat / (S - 1));
   // a fragment load of a row-major k-contiguous operand touches 32 lines, a packed one 8 (ta_x = 1 / 0.25)
   const double ta = wg_per_cu * 4 * per * (TM * ta_a + TN * ta_b) * 64.0;
-  return std::max(mfma, std::max(chain, ta)) + (WK > 1 ? 400.0 * TM * TN : 0.0) +
-         (KS > 1 ? 2400.0 + 300.0 * KS * TM * TN : 0.0);
-}
-
-// Cross-workgroup split-K factor for a chosen tile shape (CGL_SPLITK=0 disables, =N forces N):
-// KS in {1, 2, 4} with >= 2 chunks per wave and a partial slab of <= 16 KB per tile.
-int gemm_splitk_env() {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("CGL_SPLITK");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
-void choose_ks(CglGemmDesc& d) {
-  d.ksplit = 1;
-  // Measured on MI355X (tools/gemm_bench REPS 2, profiles/r01_gemm_microbench_v8_splitk.txt): the
-  // combine (publish + ticket + the reducer's read, ~2-3 us) outweighs the shorter k-loop on every
-  // GEMM of the B=256 round, so split-K is opt-in (CGL_SPLITK=N forces N; -1 = cost model).
-  const int env = gemm_splitk_env();
-  if (env == 0) return;
-  const int nch = (d.K + CGL_GEMM_KCHUNK - 1) / CGL_GEMM_KCHUNK;
-  const long slab = (long)d.WM * d.WN * d.TM * d.TN * 4096;
-  if (slab > 16384) return;
-  double best = gemm_cost(d.M, d.N, d.K, d.WM, d.WN, d.WK, d.TM, d.TN, 1);
-  for (int ks : {2, 4}) {
-    if (nch < 2 * d.WK * ks) break;
-    if (env > 0 && ks != env) continue;
-    const double c = gemm_cost(d.M, d.N, d.K, d.WM, d.WN, d.WK, d.TM, d.TN, ks);
-    if (env > 0 || c < best * 0.97) {
-      best = c;
-      d.ksplit = ks;
-    }
-  }
+  return std::max(mfma, std::max(chain, ta)) + (WK > 1 ? 400.0 * TM * TN : 0.0);
 }
 
 // force_wm: rows per wave-row group fixed (32 * TM * WM == 32 * force_wm); force_t: TM = TN fixed
-// CGL_GEMM_TILE="WM,WN,WK,T" forces one wave arrangement and block shape on every problem the
-// planner tiles freely (tile-search experiments, profiles/r02_gemm_tile_search*.txt; unset = the
-// cost model)
-bool gemm_tile_env(int* o) {
-  static int v[5] = {-1, 0, 0, 0, 0};
-  if (v[0] < 0) {
-    v[0] = 0;
-    const char* e = getenv("CGL_GEMM_TILE");
-    if (e && sscanf(e, "%d,%d,%d,%d", &v[1], &v[2], &v[3], &v[4]) == 4 && v[1] * v[2] * v[3] == 4 &&
-        (v[4] == 1 || v[4] == 2))
-      v[0] = 1;
-  }
-  for (int i = 0; i < 4; ++i) o[i] = v[i + 1];
-  return v[0] == 1;
-}
-
 void choose_tiles(CglGemmDesc& d, int force_wm = 0, int force_t = 0) {
   static const int opts[4][3] = {{2, 2, 1}, {2, 1, 2}, {1, 2, 2}, {1, 1, 4}};
   double best = 1e300;
-  int fe[4];
-  if (!force_wm && !force_t && gemm_tile_env(fe)) {
-    d.WM = fe[0];
-    d.WN = fe[1];
-    d.WK = fe[2];
-    d.TM = d.TN = fe[3];
-    d.tiles_m = (d.M + 32 * fe[3] * fe[0] - 1) / (32 * fe[3] * fe[0]);
-    d.tiles_n = (d.N + 32 * fe[3] * fe[1] - 1) / (32 * fe[3] * fe[1]);
-    return;
-  }
   for (int t = 1; t <= 2; ++t) {
     if (force_t && t != force_t) continue;
     for (auto& o : opts) {
       if (force_wm && o[0] * t != force_wm) continue;
-      const double c = gemm_cost(d.M, d.N, d.K, o[0], o[1], o[2], t, t, 1, d.a_pk ? 0.25 : 1.0, d.b_pk ? 0.25 : 1.0);
+      const double c = gemm_cost(d.M, d.N, d.K, o[0], o[1], o[2], t, t, d.a_pk ? 0.25 : 1.0, d.b_pk ? 0.25 : 1.0);
       if (c < best * (1.0 - 1e-9)) {
         best = c;
         d.WM = o[0];
@@ -544,7 +435,6 @@ struct cgl_gan {
   hipGraphExec_t gexec_k[kRoundGraphs] = {nullptr, nullptr, nullptr, nullptr};
   int gexec_kn[kRoundGraphs] = {0, 0, 0, 0};
   hipStream_t cap = nullptr;   // private capture stream (the legacy default stream cannot capture)
-  hipStream_t side = nullptr;  // second stream: the real-row D chain of the first local D step
   CglOpPack pack{};          // the round prologue's operand-packing jobs (none when pack_adam)
   CglOpPack pack_all{};      // every packing job of the plan (cgl_gan_sync_params)
   CglOpPack pack_d{};        // D's packing jobs alone (cgl_gan_sync_params_d)
@@ -558,8 +448,6 @@ struct cgl_gan {
   std::vector<int> pack_need;     // per prologue packing job: the G layer whose forward reads it (INT_MAX: backward)
   unsigned long long* trace = nullptr;   // CGL_GEMM_TRACE diagnostics buffer (kTraceWords per GEMM descriptor)
   int64_t trace_words = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};   // fork (after the prologue), join (before the D-step head)
-  bool two_streams = false;
   float* xchg = nullptr;
   int64_t xchg_n = 0;
   int xmode = 0;                     // cgl_gan_exchange_mode: 0 reduce (alpha_scale + all-reduce), 1 gathered
@@ -574,9 +462,6 @@ struct cgl_gan {
     for (auto& g : gexec_k)
       if (g) (void)hipGraphExecDestroy(g);
     if (cap) (void)hipStreamDestroy(cap);
-    if (side) (void)hipStreamDestroy(side);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
     if (trace) (void)hipFree(trace);
   }
 };
@@ -602,21 +487,6 @@ float* dgrad(const cgl_gan* c, int layer, int kind) {
   for (auto& t : c->dl)
     if (t.layer == layer && t.kind == kind) return c->bufs.d_grads + t.off;
   return nullptr;
-}
-
-// BatchNorm1d folded into the neighbouring GEMMs' operand loads instead of the cgl_bn_apply (bit 1:
-// forward, a_bn 1) / cgl_bn_bwd (bit 2: backward, a_bn 2) launches.  CGL_BN_FOLD = mask, default 0:
-// correct (the MLP GPU suite passes with either bit) but measured slower in the B = 256 round
-// (profiles/r03_bn_fold_ab.txt: 0.259 ms separate, 0.270 / 0.269 / 0.281 ms with bit 1 / 2 / both --
-// the consumer GEMMs grow by more than the launches they remove: the forward fold's prologue and
-// the backward fold's second operand stream, re-read by every column tile)
-int bn_fold_mask() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CGL_BN_FOLD");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
 }
 
 // Fragment-packed GEMM operands (cgl_pk_off): on by default, CGL_PACK=0 keeps every operand row-major.
@@ -651,31 +521,6 @@ bool gemm_tile_at_env(int i, int* o) {
     while (*q == ';' || *q == ' ') ++q;
   }
   return false;
-}
-
-// XCD blocking of the tile order (cgl_gemm_body): the pm x (8 / pm) slab cut whose L2 working set -- every
-// XCD reads A / pm and B pm / 8 -- is smallest, i.e. the least fabric traffic A pn + B pm summed over the
-// XCDs (the n-major ranges, pm = 1, read all of A on every XCD).  Measured SLOWER in the B = 256 round
-// (0.2666 vs 0.2464 ms, interleaved x3, profiles/r04_xcd_block_ab.txt): the n-major ranges keep a weight
-// panel hot in one XCD's L2 while consecutive workgroups sweep the (smaller) activation rows.  Opt-in:
-// CGL_XCD_BLOCK=-1 cost model, =1/2/4/8 that pm where the grid allows it; default 0 (n-major ranges).
-void choose_xcd(CglGemmDesc& d) {
-  static int env = -2;
-  if (env == -2) env = getenv("CGL_XCD_BLOCK") ? atoi(getenv("CGL_XCD_BLOCK")) : 0;
-  d.xcd_pm = 0;
-  if (env == 0 || (long)d.tiles_m * d.tiles_n * (d.ksplit > 1 ? d.ksplit : 1) < 16) return;
-  const double A = (double)d.M * d.K, B = (double)(d.N - (d.layout != 0 ? d.b_ones_col : 0)) * d.K;
-  double best = 1e300;
-  for (int pm : {1, 2, 4, 8}) {
-    const int pn = 8 / pm;
-    if (pm > d.tiles_m || pn > d.tiles_n) continue;
-    if (env > 0 && pm != env) continue;
-    const double c = A * pn + B * pm;
-    if (c < best * (1.0 - 1e-9)) {
-      best = c;
-      d.xcd_pm = pm;
-    }
-  }
 }
 
 void set_tiles(CglGemmDesc& d, int wm, int wn, int wk, int t) {
@@ -736,40 +581,19 @@ void push_gemm(cgl_gan* c, std::vector<Launch>& ph, std::vector<CglGemmDesc> des
   for (int i = 0; i < (int)descs.size(); ++i) {
     CglGemmDesc& d = descs[i];
     int pk[3];
-    if (i < CGL_MAX_LAYERS * 4 && isf[i] && !d.a_bn)
+    if (i < CGL_MAX_LAYERS * 4 && isf[i])
       set_tiles(d, forced[i][0], forced[i][1], forced[i][2], blk);
-    else if (blk == 1 && !d.a_bn && !getenv("CGL_GEMM_TILE") && gemm_tile_pick(d, pk))
+    else if (blk == 1 && gemm_tile_pick(d, pk))
       set_tiles(d, pk[0], pk[1], pk[2], 1);
     else if (d.TM != blk)
       choose_tiles(d, 0, blk);
   }
   L.dt = c->cfg.gemm_dtype;
   L.blk = blk;
-  long kp = 0;
-  unsigned int kc = 0;
   for (auto& d : descs) {
     set_vec(d);
-    // split-K: only on the single-stream plan (the partial / ticket regions are per launch), never
-    // under an operand transform (its prologue tables are per workgroup)
-    d.ksplit = 1;
-    if (!c->two_streams && !d.a_bn) {
-      choose_ks(d);
-      if (d.ksplit > 1 && (kp + cgl_gemm_kpart_floats(d) > kSplitKFloats ||
-                           kc + d.tiles_m * d.tiles_n > (unsigned)kSplitKCounters))
-        d.ksplit = 1;
-      if (d.ksplit > 1) {
-        d.kpart = c->ws.kpart + kp;
-        d.kcount = c->ws.kcount + kc;
-        kp += cgl_gemm_kpart_floats(d);
-        kc += d.tiles_m * d.tiles_n;
-      }
-    }
-    d.tab_floats = cgl_gemm_tab_floats(d);
-    choose_xcd(d);
-    L.abn = std::max(L.abn, d.a_bn);
     d.wg_begin = wg;
     wg += cgl_gemm_wgs(d);
-    L.sk = L.sk || d.ksplit > 1;
     const int nalg = d.b_ones_col ? d.N - 1 : d.N;
     L.flops += 2.0 * d.M * (double)nalg * d.K;
     stage = std::max(stage, cgl_gemm_stage_bytes(d));
@@ -781,9 +605,8 @@ void push_gemm(cgl_gan* c, std::vector<Launch>& ph, std::vector<CglGemmDesc> des
     for (int q = L.first; q < L.first + L.count; ++q) {
       const CglGemmDesc& d = c->gemm[q];
       fprintf(stderr, "gemm launch %zu: desc %d layout %d M %d N %d K %d WM %d WN %d WK %d TM %d TN %d tiles %dx%d "
-              "ks %d grid %d shmem %d blk %d vec %d/%d a_bn %d xcd_pm %d\n", ph.size(), q, d.layout, d.M, d.N, d.K, d.WM,
-              d.WN, d.WK, d.TM, d.TN, d.tiles_m, d.tiles_n, d.ksplit, L.grid, L.shmem, L.blk, d.a_vec, d.b_vec, d.a_bn,
-              d.xcd_pm);
+              "grid %d shmem %d blk %d vec %d/%d\n", ph.size(), q, d.layout, d.M, d.N, d.K, d.WM, d.WN, d.WK, d.TM, d.TN,
+              d.tiles_m, d.tiles_n, L.grid, L.shmem, L.blk, d.a_vec, d.b_vec);
     }
   }
   ph.push_back(L);
@@ -815,10 +638,9 @@ void push_bnb(cgl_gan* c, std::vector<Launch>& ph, const CglBnBwdDesc& b) {
   L.kind = K_BNBWD;
   L.first = (int)c->bnb.size();
   L.count = 1;
-  // features per workgroup (CGL_BNB_FPW = 32 / 16 / 8 / 4, default 8): a narrower slice gives the narrow layers
-  // more workgroups (B = 256, F = 256: 8 -> 32 workgroups; 8 measured -6 us/round vs 32, profiles/r03_bnb_ab.txt)
-  const int fe = getenv("CGL_BNB_FPW") ? atoi(getenv("CGL_BNB_FPW")) : 8;
-  L.blk = (fe == 32 || fe == 16 || fe == 4) ? fe : 8;
+  // 8 features per workgroup (cgl_bn_bwd8): the narrow slice gives the narrow layers more workgroups (B = 256,
+  // F = 256: 32 workgroups; measured -6 us/round against 32 features per workgroup, profiles/r03_bnb_ab.txt)
+  L.blk = 8;
   L.grid = (b.F + L.blk - 1) / L.blk;
   c->bnb.push_back(b);
   ph.push_back(L);
@@ -870,12 +692,12 @@ void fuse_wgrad_adam(cgl_gan* c, std::vector<Launch>& ph, int model) {
   if (!env || cf.loss_scale > 0.f || cf.gemm_dtype != CGL_DTYPE_F32 || sp.bn[0] || ph.size() < 2) return;
   Launch& G = ph[ph.size() - 2];
   Launch& A = ph.back();
-  if (G.kind != K_GEMM || G.count != 1 || G.sk || G.abn || A.kind != K_ADAM) return;
+  if (G.kind != K_GEMM || G.count != 1 || A.kind != K_ADAM) return;
   CglGemmDesc& d = c->gemm[G.first];
   const bool gm = model == CGL_MODEL_G;
   float* gw = gm ? ggrad(c, 0, 0) : dgrad(c, 0, 0);
   float* gb = gm ? ggrad(c, 0, 1) : dgrad(c, 0, 1);
-  if (d.layout != 2 || d.C != gw || d.bias_out != gb || d.ksplit > 1 || d.a_bn) return;
+  if (d.layout != 2 || d.C != gw || d.bias_out != gb) return;
   float* P = gm ? c->bufs.g_params : c->bufs.d_params;
   float* M = gm ? c->bufs.g_m : c->bufs.d_m;
   float* V = gm ? c->bufs.g_v : c->bufs.d_v;
@@ -915,7 +737,7 @@ void fuse_wgrad_adam(cgl_gan* c, std::vector<Launch>& ph, int model) {
   ph.back() = F;
 }
 
-// A head launch followed (same stream, no event between) by a GEMM launch leaves its batch-mean loss reduction
+// A head launch followed by a GEMM launch leaves its batch-mean loss reduction
 // to that launch: the head workgroups only store their partials (no release, no ticket, no last-arriver
 // round trips), and one extra workgroup of the GEMM launch -- its last -- reduces them in the same fixed
 // order (cgl_head_finish), so the losses are bitwise those of the ticket path.  The kernel boundary makes the
@@ -927,9 +749,7 @@ void defer_heads(cgl_gan* c) {
     for (size_t i = 0; i + 1 < ph->size(); ++i) {
       Launch& H = (*ph)[i];
       Launch& G = (*ph)[i + 1];
-      if (H.kind != K_HEAD || G.kind != K_GEMM || H.stream != 0 || G.stream != 0 || H.record_ev >= 0 ||
-          G.wait_ev >= 0)
-        continue;
+      if (H.kind != K_HEAD || G.kind != K_GEMM) continue;
       CglGemmDesc& d0 = c->gemm[G.first];
       if (d0.fin_head) continue;
       CglHeadDesc& h = c->head[H.first];
@@ -944,19 +764,19 @@ void defer_heads(cgl_gan* c) {
 
 // The round prologue and G's first GEMM as one launch (K_GEMM_PRO, cgl_gemm_pro): the GEMM's workgroups
 // draw their own rows of z (a_gen; every column tile of a row tile draws the same rows, identical writes),
-// the prologue's other blocks ride along.  fp32 plans on one stream; CGL_FUSE_PRO=0 keeps two launches.
+// the prologue's other blocks ride along.  fp32 plans; CGL_FUSE_PRO=0 keeps two launches.
 void fuse_prologue(cgl_gan* c) {
   const int env = getenv("CGL_FUSE_PRO") ? atoi(getenv("CGL_FUSE_PRO")) : 1;
   std::vector<Launch>& A = c->phA;
-  if (!env || c->two_streams || c->cfg.gemm_dtype != CGL_DTYPE_F32 || A.size() < 2) return;
+  if (!env || c->cfg.gemm_dtype != CGL_DTYPE_F32 || A.size() < 2) return;
   const Launch& P = A[0];
   const Launch& G = A[1];
-  if (P.kind != K_PROLOGUE || G.kind != K_GEMM || G.count != 1 || G.sk || G.abn) return;
+  if (P.kind != K_PROLOGUE || G.kind != K_GEMM || G.count != 1) return;
   CglGemmDesc& d = c->gemm[G.first];
   // (b_pk: layer 0's packed weights are written by the prologue's pack blocks, which would run in this same
   // launch with no ordering against the GEMM tiles reading them -- keep two launches then)
   if (d.layout != 0 || d.a.p0 != (c->z_ahead ? c->ws.znext : c->bufs.z) || d.a.idx0 || d.a.split != 0x7fffffff ||
-      d.a_pk || d.b_pk || d.ksplit > 1)
+      d.a_pk || d.b_pk)
     return;
   if (c->cfg.gen_z && !c->z_ahead) {
     if (d.M != 2 * c->cfg.batch || d.K != c->cfg.g.dims[0] || d.a.ld != d.K) return;   // the tiles cover every z row
@@ -974,7 +794,6 @@ void fuse_prologue(cgl_gan* c) {
   F.nb_samp = P.nb_samp;
   F.grid_y = G.grid;
   F.grid = G.grid + (P.grid - P.nb_norm);      // every prologue block but the z draw
-  F.record_ev = P.record_ev;
   A.erase(A.begin());
   A[0] = F;
 }
@@ -1234,7 +1053,7 @@ int build_plan(cgl_gan* c) {
   {
     const int zenv = getenv("CGL_Z_AHEAD") ? atoi(getenv("CGL_Z_AHEAD")) : 1;        // read per plan
     const int genv = getenv("CGL_FUSE_GADAM") ? atoi(getenv("CGL_FUSE_GADAM")) : 0;  // (its Adam rides in a GEMM)
-    c->z_ahead = cf.gen_z && zenv && !genv && !c->two_streams;
+    c->z_ahead = cf.gen_z && zenv && !genv;
   }
   // ---- round prologue: per-round scalars, z draw, real-batch sampling (one launch)
   const int* real_idx = c->bufs.real_idx;
@@ -1259,15 +1078,13 @@ int build_plan(cgl_gan* c) {
       real_idx = w.idx;
     }
     Lp.grid = 1 + Lp.nb_norm + Lp.nb_samp;
-    Lp.record_ev = c->two_streams ? 0 : -1;   // fork point of the side stream
     A.push_back(Lp);
   }
 
   // ---- G forward on [z1; z2] (2B rows; BatchNorm statistics per B-row forward call).  The
-  // BatchNorm1d(train) + LeakyReLU of a layer's output is applied by the next layer's GEMM as it
-  // loads its A operand (a_bn 1: statistics from this GEMM's per-tile partials, combined in the
-  // consumer's prologue), which also writes the activation out for the backward pass; a
-  // cgl_bn_apply launch remains for shapes the fold does not cover (and with CGL_BN_FOLD=0).
+  // BatchNorm1d(train) + LeakyReLU of a layer's output is a cgl_bn_apply launch between the two GEMMs: it
+  // combines the producer GEMM's per-tile partials and writes the activation for the next GEMM and the
+  // backward pass.
   CglBnFwd pend;
   std::memset(&pend, 0, sizeof(pend));
   bool pend_on = false;
@@ -1300,33 +1117,24 @@ int build_plan(cgl_gan* c) {
       e.b_pk = 1;
     }
     if (pend_on) {
-      const int bm = 32 * e.TM * e.WM;
-      if ((bn_fold_mask() & 1) && cf.gemm_dtype == CGL_DTYPE_F32 && fi <= CGL_BN_MAXF && B % bm == 0) {
-        e.a_bn = 1;
-        e.a_bnf = pend;
-        e.a_copy = w.gact[l - 1];        // the activation, for the backward pass (both calls' rows)
-        e.a_copy_ld = fi;
-        e.a_copy_row0 = 0;
-      } else {
-        CglBnApplyDesc ap;
-        std::memset(&ap, 0, sizeof(ap));
-        ap.F = fi;
-        ap.Y = w.gout[l - 1];
-        ap.ld_y = fi;
-        ap.act = w.gact[l - 1];
-        ap.ld_act = fi;
-        ap.bn = pend;
-        if (pk_on) {
-          ap.act_pk = w.gpk[l - 1];
-          e.a_pk = 1;
-        }
-        push_bna(c, A, ap);
-        A.back().layer = l;
-        e.a = rows(e.a_pk ? w.gpk[l - 1] : w.gact[l - 1], fi);
+      CglBnApplyDesc ap;
+      std::memset(&ap, 0, sizeof(ap));
+      ap.F = fi;
+      ap.Y = w.gout[l - 1];
+      ap.ld_y = fi;
+      ap.act = w.gact[l - 1];
+      ap.ld_act = fi;
+      ap.bn = pend;
+      if (pk_on) {
+        ap.act_pk = w.gpk[l - 1];
+        e.a_pk = 1;
       }
+      push_bna(c, A, ap);
+      A.back().layer = l;
+      e.a = rows(e.a_pk ? w.gpk[l - 1] : w.gact[l - 1], fi);
       pend_on = false;
     }
-    if ((e.a_pk || e.b_pk) && !(l + 1 < L && g.bn[l] && B < 64) && !e.a_bn) choose_tiles(e);
+    if ((e.a_pk || e.b_pk) && !(l + 1 < L && g.bn[l] && B < 64)) choose_tiles(e);
     e.a_vec = (fi % 4 == 0) && al16(e.a.p0);
     e.b = rows(e.b_pk ? w.wpk[l] : gparam(c, l, 0), fi);
     e.b_vec = (fi % 4 == 0);
@@ -1370,41 +1178,33 @@ int build_plan(cgl_gan* c) {
   // ---- local D steps (Worker.train capgan.py:324-341)
   const int C = d.dims[J];
   const float combine = cf.loss == CGL_LOSS_CE2 ? 0.5f : 1.0f;
-  // hidden-layer forwards of the D-step input rows [row0, row0 + nrows): part 0 = real rows
-  // (through the sampler's index list), part 1 = Xd rows, part 2 = both (one 2-segment GEMM)
+  // hidden-layer forwards of the D-step input rows: the real rows (through the sampler's index list) and
+  // the Xd rows as one 2-segment GEMM
   plan_d_pack(c);
-  auto d_forward = [&](int ep, int part, int stream, int wait_ev) {
-    const int row0 = part == 1 ? Br : 0;
-    const int nrows = part == 0 ? Br : part == 1 ? B : Md;
+  auto d_forward = [&](int ep) {
     for (int j = 0; j + 1 < J; ++j) {
       const int fi = d.dims[j], fo = d.dims[j + 1];
-      CglGemmDesc e = make_gemm(0, nrows, fo, fi);
+      CglGemmDesc e = make_gemm(0, Md, fo, fi);
       if (j == 0) {
         CglRowSrc r;
         std::memset(&r, 0, sizeof(r));
         r.split = 0x7fffffff;
         r.ld = fi;
-        if (part == 1) {
-          r.p0 = Xd;
+        if (real_idx) {
+          r.p0 = c->bufs.real;
+          r.idx0 = real_idx + (int64_t)ep * Br;
         } else {
-          if (real_idx) {
-            r.p0 = c->bufs.real;
-            r.idx0 = real_idx + (int64_t)ep * Br;
-          } else {
-            r.p0 = c->bufs.real + (int64_t)ep * Br * fi;
-          }
-          if (part == 2) {
-            r.p1 = Xd;
-            r.split = Br;
-          }
+          r.p0 = c->bufs.real + (int64_t)ep * Br * fi;
         }
+        r.p1 = Xd;
+        r.split = Br;
         e.a = r;
         e.a_vec = (fi % 4 == 0) && al16(c->bufs.real) && al16(Xd);
-        e.a_copy = w.R + (int64_t)row0 * fi;
+        e.a_copy = w.R;
         e.a_copy_ld = fi;
         e.a_copy_row0 = 0;
       } else {
-        e.a = rows(w.P[j - 1] + (int64_t)row0 * fi, fi);
+        e.a = rows(w.P[j - 1], fi);
         e.a_vec = (fi % 4 == 0);
       }
       e.b = rows(dparam(c, j, 0), fi);
@@ -1418,68 +1218,48 @@ int build_plan(cgl_gan* c) {
       e.bias = dparam(c, j, 1);
       e.act = CGL_EPI_ACT_LEAKY;
       e.slope = sl;
-      e.C = w.P[j] + (int64_t)row0 * fo;
+      e.C = w.P[j];
       e.ldc = fo;
       push_gemm(c, A, {e});
-      A.back().stream = stream;
-      if (j == 0) A.back().wait_ev = wait_ev;
     }
   };
-  // the loss head of a part: CE/BCE on the logits, dlogits and the gradient into the last
+  // the loss head: CE/BCE on the logits, dlogits and the gradient into the last
   // hidden layer; real rows are segment 0 (target valid), Xd rows segment 1 (target fake)
-  auto d_head = [&](int ep, int part, int stream, int wait_ev, int record_ev) {
-    const int row0 = part == 1 ? Br : 0;
-    const int nrows = part == 0 ? Br : part == 1 ? B : Md;
+  auto d_head = [&](int ep) {
     const int F = d.dims[J - 1];
     CglHeadDesc h;
     std::memset(&h, 0, sizeof(h));
-    h.M = nrows;
+    h.M = Md;
     h.F = F;
     h.C = C;
     h.loss = cf.loss;
-    h.P = w.P[J - 2] + (int64_t)row0 * F;
+    h.P = w.P[J - 2];
     h.ldp = F;
     h.W = dparam(c, J - 1, 0);
     h.b = dparam(c, J - 1, 1);
-    h.split = part == 0 ? Br : part == 1 ? 0 : Br;
+    h.split = Br;
     h.t0 = 1;
     h.t1 = 0;
     h.w0 = combine / Br;
     h.w1 = combine / B;
-    h.dlogits = w.dlog + (int64_t)row0 * C;
-    h.dP = w.dQ[J - 2] + (int64_t)row0 * F;
+    h.dlogits = w.dlog;
+    h.dP = w.dQ[J - 2];
     h.lddp = F;
     h.slope = sl;
-    h.part = part == 0 ? w.hpart2 : w.hpart;
-    h.counter = w.counters + (part == 0 ? 16 : ep);
-    if (cf.sample_n > 0 && part != 1) h.n0_dev = &st->real_rows[ep];   // the sampler's short batch
+    h.part = w.hpart;
+    h.counter = w.counters + ep;
+    if (cf.sample_n > 0) h.n0_dev = &st->real_rows[ep];   // the sampler's short batch
     h.loss_out0 = &st->d_loss_parts[ep][0];
     h.loss_out1 = &st->d_loss_parts[ep][1];
     h.combine = combine;
-    h.combine_out = part == 0 ? nullptr : &st->d_loss[ep];
-    h.combine_in0 = part == 1 ? &st->d_loss_parts[ep][0] : nullptr;
+    h.combine_out = &st->d_loss[ep];
     h.scale_dev = scaling ? &st->scale[0] : nullptr;
     h.rows_per_wg = kHeadRows;
     push_head(c, A, h);
-    A.back().stream = stream;
-    A.back().wait_ev = wait_ev;
-    A.back().record_ev = record_ev;
   };
   for (int ep = 0; ep < cf.epoch; ++ep) {
-    if (ep == 0 && c->two_streams) {
-      // the real rows of the first local D step do not depend on G: their forward and loss
-      // head run on the side stream concurrently with the G forward (forked after the
-      // prologue, joined before the Xd head, whose D_loss combines both segments)
-      d_forward(0, 0, 1, 0);
-      d_head(0, 0, 1, -1, 1);
-      // (the G forward was pushed before; move the side chain in front of it in list order so
-      // that a single-stream replay of the list is still a valid order)
-      d_forward(0, 1, 0, -1);
-      d_head(0, 1, 0, 1, -1);
-    } else {
-      d_forward(ep, 2, 0, -1);
-      d_head(ep, 2, 0, -1, -1);
-    }
+    d_forward(ep);
+    d_head(ep);
     // backward: weight grads (TN, + bias column) and input grads (NN, LeakyReLU' mask)
     for (int j = J - 1; j >= 0; --j) {
       std::vector<CglGemmDesc> grp;
@@ -1607,43 +1387,14 @@ int build_plan(cgl_gan* c) {
     c->xchg_n = (int64_t)B * img;
     ph = &Bp;
   }
-  // The BatchNorm1d backward of layer l - 1 is folded into the GEMMs around it (a_bn 2): the
-  // input-gradient GEMM of layer l stores dy = dA * LeakyReLU'(post) with per-tile {sum dy,
-  // sum (y - mean) dy} partials, and layer l - 1's weight- and input-gradient GEMMs apply the
-  // BatchNorm backward as they load dy (their k-contiguous problem also writes dgamma / dbeta).
-  // Not at the Mix-G exchange point (the all-reduce of dA sits between the two), and a cgl_bn_bwd
-  // launch where no input-gradient problem follows (and with CGL_BN_FOLD=0).
+  // The BatchNorm1d backward of layer l - 1 (with the LeakyReLU' mask of its output) is a cgl_bn_bwd launch
+  // between layer l's input-gradient GEMM and layer l - 1's GEMMs.
   auto gbuf = [&](int l) -> float* { return l == L - 1 ? w.dYL : w.gG[l]; };
   bool gG_packed[CGL_MAX_LAYERS] = {};   // gG[l] has a packed copy (written by cgl_bn_bwd)
-  CglBnBwdFold gfold;
-  std::memset(&gfold, 0, sizeof(gfold));
-  bool gfold_on = false;          // layer l's output gradient is dy in gdA[l] + partials
   for (int l = L - 1; l >= 0; --l) {
     std::vector<CglGemmDesc> grp;
     const int fi = g.dims[l], fo = g.dims[l + 1];
-    const float* gA = gfold_on ? w.gdA[l] : gbuf(l);
-    if (gfold_on && l == 0) {     // no input-gradient problem to carry the fold: the launch
-      CglBnBwdDesc b;             // (dy already masked: no post)
-      std::memset(&b, 0, sizeof(b));
-      b.M = B;
-      b.F = fo;
-      b.dA = w.gdA[l];
-      b.ld_da = fo;
-      b.Y = gfold.y;
-      b.ld_y = fo;
-      b.mean = gfold.mean;
-      b.invstd = gfold.invstd;
-      b.gamma = gfold.gamma;
-      b.dZ = w.gG[l];
-      b.ld_dz = fo;
-      b.g_gamma = gfold.g_gamma;
-      b.g_beta = gfold.g_beta;
-      b.slope = sl;
-      if (scaling) b.inf_flag = &st->found[1];
-      push_bnb(c, *ph, b);
-      gfold_on = false;
-      gA = gbuf(l);
-    }
+    const float* gA = gbuf(l);
     {
       const float* prev;
       if (l == 0)
@@ -1660,17 +1411,12 @@ int build_plan(cgl_gan* c) {
       t.ldc = fi;
       t.bias_out = ggrad(c, l, 1);
       if (scaling) t.inf_flag = &st->found[1];
-      if (gfold_on) {
-        t.a_bn = 2;
-        t.a_bnb = gfold;
-      }
       grp.push_back(t);
     }
-    bool fold_next = false;
     if (l >= 1) {
       // dA = dZ W_l: NN on the row-major W, or NT on its packed transpose P(W_l^T) (round prologue)
       // with dZ packed too when cgl_bn_bwd wrote it
-      const bool pk = pack_enabled() && !gfold_on && c->pack.nj < CGL_PACK_MAXJ;
+      const bool pk = pack_enabled() && c->pack.nj < CGL_PACK_MAXJ;
       CglGemmDesc n = make_gemm(pk ? 0 : 1, B, fi, fo);
       n.a = rows(gA, fo);
       n.a_vec = (fo % 4 == 0);
@@ -1694,22 +1440,8 @@ int build_plan(cgl_gan* c) {
       }
       n.slope = sl;
       n.ldc = fi;
-      if (gfold_on) {
-        n.a_bn = 2;
-        n.a_bnb = gfold;
-      }
       if (g.bn[l - 1]) {
         n.C = w.gdA[l - 1];
-        fold_next = (bn_fold_mask() & 2) && cf.gemm_dtype == CGL_DTYPE_F32 && cf.exchange_layer != l &&
-                    fi <= CGL_BN_MAXF;
-        if (fold_next) {
-          n.mask_ref = w.gact[l - 1] + (int64_t)B * fi;    // LeakyReLU' of the BatchNorm output
-          n.mask_ld = fi;
-          n.bnb_part = w.gdpart[l - 1];
-          n.bnb_y = w.gout[l - 1] + (int64_t)B * fi;       // the Xg call's BatchNorm input
-          n.bnb_ld = fi;
-          n.bnb_mean = w.gmean[l - 1] + fi;                // group 1 = the Xg forward call
-        }
       } else {
         n.mask_ref = w.gout[l - 1] + (int64_t)B * fi;
         n.mask_ld = fi;
@@ -1718,27 +1450,12 @@ int build_plan(cgl_gan* c) {
       grp.push_back(n);
     }
     push_gemm(c, *ph, grp);
-    gfold_on = false;
-    if (fold_next) {
-      gfold.part = w.gdpart[l - 1];
-      gfold.tiles = c->gemm.back().tiles_m;
-      gfold.F = fi;
-      gfold.M = B;
-      gfold.mean = w.gmean[l - 1] + fi;
-      gfold.invstd = w.ginvstd[l - 1] + fi;
-      gfold.gamma = gparam(c, l - 1, 2);
-      gfold.g_gamma = ggrad(c, l - 1, 2);
-      gfold.g_beta = ggrad(c, l - 1, 3);
-      gfold.y = w.gout[l - 1] + (int64_t)B * fi;
-      gfold.ldy = fi;
-      gfold_on = true;
-    }
     if (l >= 1 && cf.exchange_layer == l) {
       c->xchg = g.bn[l - 1] ? w.gdA[l - 1] : w.gG[l - 1];
       c->xchg_n = (int64_t)B * fi;
       ph = &Bp;
     }
-    if (l >= 1 && g.bn[l - 1] && !fold_next) {
+    if (l >= 1 && g.bn[l - 1]) {
       CglBnBwdDesc b;
       std::memset(&b, 0, sizeof(b));
       b.M = B;
@@ -1835,15 +1552,7 @@ CglGemmSel gemm_prefetch(const cgl_gan* c, const Launch& L) {
   return q;
 }
 
-int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s_main, bool events = true) {
-  hipStream_t s = s_main;
-  if (events && c->two_streams) {
-    if (L.stream == 1) s = c->side;
-    if (L.wait_ev >= 0) {
-      const hipError_t ew = hipStreamWaitEvent(s, c->ev[L.wait_ev], 0);
-      if (ew != hipSuccess) return (int)ew;
-    }
-  }
+int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s) {
   switch (L.kind) {
     case K_GEMM:
       if (L.count > 3) return CGL_E_SIZE;
@@ -1852,7 +1561,7 @@ int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s_main, bool events = t
       const CglGemmSel pq = gemm_prefetch(c, L);
       q.pf = pq.pf;
       q.pf_lines = pq.pf_lines;
-      launch_gemm(L.blk, L.grid, L.shmem, s, c->ws.gemm + L.first, q, L.sk, L.dt, L.abn);
+      launch_gemm(L.blk, L.grid, L.shmem, s, c->ws.gemm + L.first, q, L.dt);
       break;
     }
     case K_HEAD:
@@ -1874,14 +1583,7 @@ int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s_main, bool events = t
         klaunch(cgl_bn_apply, dim3(L.grid, L.grid_y), dim3(256), 0, s, c->bna[L.first]);
       break;
     case K_BNBWD:
-      if (L.blk == 16)
-        klaunch(cgl_bn_bwd16, dim3(L.grid), dim3(256), 0, s, c->bnb[L.first]);
-      else if (L.blk == 8)
-        klaunch(cgl_bn_bwd8, dim3(L.grid), dim3(256), 0, s, c->bnb[L.first]);
-      else if (L.blk == 4)
-        klaunch(cgl_bn_bwd4, dim3(L.grid), dim3(256), 0, s, c->bnb[L.first]);
-      else
-        klaunch(cgl_bn_bwd, dim3(L.grid), dim3(256), 0, s, c->bnb[L.first]);
+      klaunch(cgl_bn_bwd8, dim3(L.grid), dim3(256), 0, s, c->bnb[L.first]);
       break;
     case K_ADAM:
       if (L.adpk)
@@ -1922,8 +1624,7 @@ int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s_main, bool events = t
     default:
       return CGL_E_STATE;
   }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && events && c->two_streams && L.record_ev >= 0) e = hipEventRecord(c->ev[L.record_ev], s);
+  const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -2016,21 +1717,6 @@ int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_g
   }
   cgl_gan* c = new cgl_gan();
   c->cfg = *cfg;
-  {
-    // measured slower on MI355X (0.299 vs 0.264 ms per B=256 round: the concurrent chains slow
-    // each other and the fork / join add latency), so opt-in only
-    const char* e2 = getenv("CGL_TWO_STREAMS");
-    c->two_streams = e2 && atoi(e2) != 0 && cfg->d.n_layers >= 2;
-  }
-  if (c->two_streams) {
-    hipError_t es = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
-    if (es == hipSuccess) es = hipEventCreateWithFlags(&c->ev[0], hipEventDisableTiming);
-    if (es == hipSuccess) es = hipEventCreateWithFlags(&c->ev[1], hipEventDisableTiming);
-    if (es != hipSuccess) {
-      delete c;
-      return (int)es;
-    }
-  }
   c->bufs = *bufs;
   c->ws = carve_ws(*cfg, bufs->workspace);
   c->gl = param_layout(cfg->g, nullptr);
@@ -2075,7 +1761,6 @@ int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_g
   if (he == hipSuccess && !c->bnb.empty())
     he = hipMemcpy(c->ws.bnb, c->bnb.data(), c->bnb.size() * sizeof(CglBnBwdDesc), hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemset(c->ws.counters, 0, kCounters * sizeof(unsigned int));
-  if (he == hipSuccess) he = hipMemset(c->ws.kcount, 0, kSplitKCounters * sizeof(unsigned int));
   if (he == hipSuccess) he = hipMemset(c->ws.st, 0, sizeof(CglStepState));
   if (he == hipSuccess) he = hipMemset(c->ws.rlog, 0, CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec));
   if (he == hipSuccess && c->z_ahead) {   // round 1's z
@@ -2114,7 +1799,6 @@ int cgl_gan_reset(cgl_gan* c, const float* beta_host, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipMemcpyAsync(c->ws.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(c->ws.counters, 0, kCounters * sizeof(unsigned int), s));
-  HIPCHK(hipMemsetAsync(c->ws.kcount, 0, kSplitKCounters * sizeof(unsigned int), s));
   HIPCHK(hipMemsetAsync(c->ws.rlog, 0, CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec), s));   // a new timeline
   if ((c->pack_adam || c->d_pack) && c->pack_all.blocks > 0) {   // the packed weights from the current parameters
     hipLaunchKernelGGL(cgl_pack_all, dim3(c->pack_all.blocks), dim3(256), 0, s, c->pack_all);
@@ -2492,7 +2176,7 @@ int cgl_gan_launch_one(cgl_gan* c, int phase, int idx, void* stream) {
   if (!c || phase < 0 || phase > 2 || idx < 0 || idx >= cgl_gan_launch_count(c, phase)) return CGL_E_ARG;
   int li;
   const std::vector<Launch>* v = phase_list(c, phase, idx, &li);
-  return exec_launch(c, (*v)[li], (hipStream_t)stream, false);
+  return exec_launch(c, (*v)[li], (hipStream_t)stream);
 }
 
 // ---------------- single ops -------------------------------------------------------------
@@ -2505,8 +2189,6 @@ static int single_gemm(CglGemmDesc& d, void*, int64_t, hipStream_t s) {
   HIPCHK(gemm_lds_attr());
   d.wg_begin = 0;
   set_vec(d);
-  d.ksplit = 1;
-  choose_xcd(d);
   const int grid = cgl_gemm_wgs(d), shmem = cgl_gemm_stage_bytes(d);
   if (d.TM == 2)
     klaunch(cgl_gemm_f32_arg<2, 2>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d);
@@ -2605,8 +2287,6 @@ int linear_prepare(int op, const float* A, const float* B, const int* b_rows, co
   }
   d.wg_begin = 0;
   set_vec(d);
-  d.ksplit = 1;
-  choose_xcd(d);
   // the descriptor buffer may have been allocated / zeroed on a non-blocking stream that the null
   // stream's copy does not wait for: drain the device so that no pending fill overwrites it
   HIPCHK(hipDeviceSynchronize());
