@@ -35,7 +35,8 @@ EXPORTS = [
     "cgl_bn2d_workspace_bytes", "cgl_bn2d_fwd", "cgl_bn2d_bwd", "cgl_act_drop_bwd", "cgl_act_drop_bwd_colsum", "cgl_colsum_finalize", "cgl_dropout2d_mask", "cgl_dropout2d_masks",
     "cgl_nchw_to_nhwc", "cgl_nhwc_to_nchw", "cgl_dense1_bwd_data_nhwc", "cgl_dense1_fwd_nhwc", "cgl_dense1_head_nhwc", "cgl_adv_loss", "cgl_adam_multi", "cgl_dense_workspace_bytes",
     "cgl_dense_fwd", "cgl_dense_bwd_data", "cgl_dense_bwd_weight", "cgl_gather_rows", "cgl_weights_scale",
-    "cgl_conv_packed_floats", "cgl_conv_pack_multi", "cgl_conv_batch_begin", "cgl_conv_batch_end", "cgl_conv_wgrad_defer_begin", "cgl_conv_wgrad_defer_end", "cgl_conv_wgrad_defer_counters", "cgl_conv3x3_bias_by_colsum", "cgl_conv3x3_fwd_packed", "cgl_conv3x3_bwd_data_packed",
+    "cgl_conv_packed_floats", "cgl_conv_pack_multi", "cgl_conv_batch_begin", "cgl_conv_batch_end", "cgl_conv_wgrad_defer_begin", "cgl_conv_wgrad_defer_end", "cgl_conv_wgrad_defer_counters", "cgl_conv3x3_bias_by_colsum",
+    "cgl_conv_wgrad_defer_cancel", "cgl_conv_wgrad_defer_log", "cgl_conv_round_log", "cgl_conv_round_log_capacity", "cgl_conv_read_round_log", "cgl_conv3x3_fwd_packed", "cgl_conv3x3_bwd_data_packed",
     "cgl_dense_fwd_packed", "cgl_dense_bwd_data_packed", "cgl_conv3x3_stat_chunks", "cgl_conv3x3_fwd_packed_stats",
     "cgl_bn2d_fwd_stats", "cgl_bn2d_fwd_stats_coef", "cgl_conv3x3_fwd_packed_bnin", "cgl_bn2d_stats_scratch_bytes", "cgl_linear_desc_bytes", "cgl_linear_prepare", "cgl_linear_prepare_gather", "cgl_linear_prepare_wgrad_nhwc",
     "cgl_linear_launch", "cgl_conv3x3_bwd_stat_chunks", "cgl_conv3x3_bwd_data_packed_stats", "cgl_conv3x3_bwd_data_stats", "cgl_bn2d_bwd_stats",
@@ -96,6 +97,23 @@ class GanRoundRec(ctypes.Structure):
                 ("F", ctypes.c_float), ("lambda_", ctypes.c_float), ("real_rows", ctypes.c_int * 8),
                 ("loss_scale", ctypes.c_float * 2), ("step_skipped", ctypes.c_int * 2),
                 ("reserved_", ctypes.c_int * 7)]
+
+
+class ConvRoundRec(ctypes.Structure):
+    """cgl_conv_round_rec: one completed conv round's scalars in the device round log (64 bytes)."""
+    _fields_ = [("round", ctypes.c_int), ("d_real", ctypes.c_float), ("d_fake", ctypes.c_float),
+                ("d_loss", ctypes.c_float), ("g_loss", ctypes.c_float), ("alpha", ctypes.c_float),
+                ("F", ctypes.c_float), ("lambda_", ctypes.c_float), ("real_rows", ctypes.c_int),
+                ("g_step", ctypes.c_int), ("d_step", ctypes.c_int), ("reserved_", ctypes.c_int * 5)]
+
+
+class ConvRoundLogArgs(ctypes.Structure):
+    """cgl_conv_round_log_args: what the conv round's record is computed from."""
+    _fields_ = [("ring", ctypes.c_void_p), ("lam_dev", ctypes.c_void_p), ("lbuf", ctypes.c_void_p),
+                ("nv", ctypes.c_void_p), ("losses_all", ctypes.c_void_p), ("alpha_all", ctypes.c_void_p),
+                ("counters", ctypes.c_void_p), ("n_workers", ctypes.c_int), ("rank", ctypes.c_int),
+                ("weighting", ctypes.c_int), ("half", ctypes.c_float), ("round", ctypes.c_int),
+                ("g_step", ctypes.c_int), ("d_step", ctypes.c_int)]
 
 
 def _hip_runtimes():
@@ -196,6 +214,11 @@ def _load():
         "cgl_conv_wgrad_defer_begin": (ci, []),
         "cgl_conv_wgrad_defer_end": (ci, [vp]),
         "cgl_conv_wgrad_defer_counters": (ci, [vp, ci, ci, vp, ci]),
+        "cgl_conv_wgrad_defer_cancel": (ci, []),
+        "cgl_conv_wgrad_defer_log": (ci, [P(ConvRoundLogArgs)]),
+        "cgl_conv_round_log": (ci, [P(ConvRoundLogArgs), vp]),
+        "cgl_conv_round_log_capacity": (ci, []),
+        "cgl_conv_read_round_log": (ci, [vp, ci, ci, P(ConvRoundRec), vp]),
         "cgl_conv3x3_fwd_packed": (ci, [vp, vp, vp, vp] + [ci] * 8 + [cf, vp, vp, i64, vp]),
         "cgl_conv3x3_bwd_data_packed": (ci, [vp, vp, vp, vp] + [ci] * 7 + [vp, i64, vp]),
         "cgl_conv3x3_stat_chunks": (i64, [ci] * 8),

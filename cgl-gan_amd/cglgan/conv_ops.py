@@ -539,6 +539,36 @@ def defer_counters(counters, snap, snap_index, v=1):
             "cgl_conv_wgrad_defer_counters")
 
 
+def round_log_args(ring, lam_dev, lbuf, nv, n_workers, rank, weighting, half, losses_all=None, alpha_all=None,
+                   counters=None, round=0, g_step=0, d_step=0):
+    """cgl_conv_round_log_args for ``round_log``: device buffers (ring int32 [cap * 16], lam_dev float [>= 1], lbuf,
+    nv; losses_all / alpha_all with n_workers > 1) and either ``counters`` (device int32 round, G steps, D steps
+    before the round's advance) or the host integers of the completed round."""
+    _chk(lam_dev, lbuf, losses_all, alpha_all)
+    if not (ring.is_cuda and ring.dtype == torch.int32 and ring.numel() >= 16 * C.lib.cgl_conv_round_log_capacity()):
+        raise ValueError("round log ring: int32 device tensor of capacity * 16 words")
+    a = C.ConvRoundLogArgs()
+    a.ring, a.lam_dev, a.lbuf, a.nv = ring.data_ptr(), lam_dev.data_ptr(), lbuf.data_ptr(), nv.data_ptr()
+    a.losses_all = losses_all.data_ptr() if losses_all is not None else None
+    a.alpha_all = alpha_all.data_ptr() if alpha_all is not None else None
+    a.counters = counters.data_ptr() if counters is not None else None
+    a.n_workers, a.rank, a.weighting, a.half = int(n_workers), int(rank), WEIGHTING[weighting], float(half)
+    a.round, a.g_step, a.d_step = int(round), int(g_step), int(d_step)
+    return a
+
+
+def round_log(args, **host):
+    """The conv round's log record and the device lambda's step (cgl_conv_round_rec): inside wgrad_defer it rides in
+    the deferred launch (cgl_conv_wgrad_defer_log, no launch added), otherwise a one-workgroup launch of its own
+    (cgl_conv_round_log).  ``host``: round / g_step / d_step of the completed round when args has no counters."""
+    for k, v in host.items():
+        setattr(args, k, int(v))
+    if _WDEFER:
+        C.check(C.lib.cgl_conv_wgrad_defer_log(ctypes.byref(args)), "cgl_conv_wgrad_defer_log")
+    else:
+        C.check(C.lib.cgl_conv_round_log(ctypes.byref(args), _s()), "cgl_conv_round_log")
+
+
 def counters_add(counters, v=1):
     """counters (device int32) += v, stream-ordered."""
     C.check(C.lib.cgl_counters_add(_p(counters), counters.numel(), int(v), _s()), "cgl_counters_add")

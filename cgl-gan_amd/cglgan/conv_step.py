@@ -22,6 +22,7 @@ state-dict order, exposed as views under the reference's keys (``l1.0.weight``,
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from collections import OrderedDict
@@ -197,9 +198,10 @@ class ConvGanStep:
         # the D-step kernels leave the padding images of a short call out (nvalid)
         self.nv = self.dstate[3:4]
         self.nv.fill_(batch)
+        self._nv_stale = False                # nv holds an explicit short batch's count that no later round rewrote
         self._dstate_host = (0, 0, 0)         # host mirror of dstate after the last issued round
         self._cuda_graph = None
-        self._kgraphs = {}             # rounds -> graph of that many whole rounds (run_rounds)
+        self._kgraphs = OrderedDict()  # rounds -> graph of that many whole rounds (run_rounds), the newest 4
         self._phase_graphs = None      # (phase A, phase B) graphs of the split round (N > 1)
         self._split_graph = False
         self._graph_delta = None
@@ -346,6 +348,23 @@ class ConvGanStep:
                 raise ValueError("data must be a [n >= 1, 1024] tensor of 32x32 images")
             if not data.is_cuda or data.dtype != torch.float32:
                 raise ValueError("data must be float32 on the GPU")
+        # device round log: a ring of cgl_conv_round_rec (64 bytes each; round r in slot (r - 1) % capacity) that the
+        # G backward's deferred launch writes every round -- the launch that advances dstate, by the same workgroup --
+        # so the rounds inside a run_rounds graph stay readable one by one (losses_log).  `rblk` is the round block:
+        # word 0 the device lambda, which that workgroup reads (F) and advances as _lam_step does on the host;
+        # `alpha_all` every worker's alpha of this round (the exchange's weights_scale writes it, N > 1).
+        # Allocated last, so that every other buffer of the step sits where it sat before the log existed
+        self.rlog = torch.zeros(16 * C.lib.cgl_conv_round_log_capacity(), dtype=torch.int32, device=dev)
+        self.rblk = torch.zeros(16, dtype=torch.float32, device=dev)
+        self.alpha_all = torch.zeros(max(n_workers, 1), dtype=torch.float32, device=dev)
+        self._lam_dev = 0.0                   # host mirror of rblk[0] after the last issued round
+        self._log_host = None
+        multi = n_workers > 1
+        self._log_args = O.round_log_args(self.rlog, self.rblk, self.lbuf, self.nv, max(n_workers, 1), rank, weighting,
+                                          0.5 if loss == "mse" else 1.0,
+                                          losses_all=self.losses_all if multi else None,
+                                          alpha_all=self.alpha_all if multi else None,
+                                          counters=self.dstate if graph else None)
 
     # ------------------------------------------------------------------ state
     def set_beta(self, beta=None):
@@ -402,6 +421,8 @@ class ConvGanStep:
         self._perm = perm.to(self.device) if perm.numel() else None
         self._gen.set_state(sd["sampler.gen"])
         self._dstate_host = None            # rewritten from the host state by the next round
+        self._lam_dev = None                # ... and the device lambda
+        self.rlog.zero_()                   # the records belong to the timeline that was running here
         torch.cuda.current_stream().synchronize()
 
     # ------------------------------------------------------------------ pieces
@@ -418,8 +439,9 @@ class ConvGanStep:
         if take < B:
             idx = torch.cat([idx, idx[:1].expand(B - take)])
         O.gather_rows(self.data, idx, 0, B, 1024, self.x3)
-        if self.short:
+        if self.short or self._nv_stale:
             self.nv.fill_(take)
+            self._nv_stale = False
         self._pos += take
 
     def _g_forward(self):
@@ -616,10 +638,19 @@ class ConvGanStep:
                 O.conv3x3_bwd_data(self.dc[0], P[ck + ".weight"], dx, n, hw, hw, ci, co, 2, 0, wp=self.pk[ck + "b"])
 
     def _g_backward(self, counters=False):
+        # the round's log record rides in the deferred launch (the workgroup that advances the counters writes it
+        # too); without that launch (CGL_CONV_WDEFER=0) it is a one-workgroup launch of its own, after the pass.
+        # Graph rounds take the round and step counts from dstate (not yet advanced), eager rounds from the host
+        self._sync_lam()
+        host = {} if self.graph else dict(round=self.round + 1, g_step=self.G.step + 1, d_step=self.D.step)
         with O.wgrad_defer(self.wdefer):
             self._g_backward_ops()
             if counters:     # round, G steps, D steps += 1 in the deferred launch; G's completed steps -> dstate[4]
                 O.defer_counters(self.dstate[0:3], self.dstate[4:5], 1)
+            if self.wdefer:
+                O.round_log(self._log_args, **host)
+        if not self.wdefer:
+            O.round_log(self._log_args, **host)
 
     def _g_backward_ops(self):
         P, G, B = self.G.params, self.G.grads, self.B
@@ -716,8 +747,9 @@ class ConvGanStep:
                 O.gather_rows(real, torch.zeros(B - nr, dtype=torch.int32, device=self.device), 0, B - nr, 1024,
                               self.x3[nr:])
             self._short_call = nr < B or self.short
-            if self._short_call:
+            if self._short_call or self._nv_stale:     # (stale: the round log records nv of full batches too)
                 self.nv.fill_(nr)
+                self._nv_stale = nr < B
         elif self.data is not None:
             if self.graph:
                 O.sample_rows_dev(self.data, B, self.seed + 1 + self.rank, self.dstate[0:1], self.x3,
@@ -770,6 +802,7 @@ class ConvGanStep:
                     O.counters_add(self.dstate[0:3], 1)     # round, G steps, D steps (epoch = 1)
                 self._dstate_host = (self.round + 1, self.G.step, self.D.step)
         self._lam_step()
+        self._lam_dev = self.lam
         self.round += 1
 
     def _lam_step(self):
@@ -805,9 +838,7 @@ class ConvGanStep:
             for _ in range(rounds):
                 self.run()
             return
-        g = self._kgraphs.get(rounds)
-        if g is None:
-            g = self._kgraphs[rounds] = self._capture_rounds(rounds)
+        g = self._kgraph(rounds)
         self._sync_dstate()
         g.replay()
         for _ in range(rounds):
@@ -815,8 +846,22 @@ class ConvGanStep:
 
     def prepare_rounds(self, rounds: int):
         """Capture the ``rounds``-round graph ahead of its first use (graph=True, N = 1, after the first round)."""
-        if self.graph and self.data is not None and self.round > 0 and rounds > 1 and rounds not in self._kgraphs:
-            self._kgraphs[rounds] = self._capture_rounds(rounds)
+        if self.graph and self.data is not None and self.round > 0 and rounds > 1:
+            self._kgraph(rounds)
+
+    KGRAPHS_MAX = 4     # cached multi-round graphs (each holds a private memory pool)
+
+    def _kgraph(self, rounds):
+        """The ``rounds``-round graph: captured on first use, the KGRAPHS_MAX newest counts kept (oldest first out:
+        a runner's remainder chunks would otherwise grow the cache, one memory pool each, without bound)."""
+        g = self._kgraphs.get(rounds)
+        if g is None:
+            if len(self._kgraphs) >= self.KGRAPHS_MAX:
+                torch.cuda.current_stream().synchronize()     # (no replay of a dropped graph is still running)
+            while len(self._kgraphs) >= self.KGRAPHS_MAX:
+                self._kgraphs.popitem(last=False)
+            g = self._kgraphs[rounds] = self._capture_rounds(rounds)
+        return g
 
     def _capture_rounds(self, rounds):
         if self._graph_delta is None:
@@ -833,7 +878,7 @@ class ConvGanStep:
         self.round, self.G.step, self.D.step = before[0], before[1], before[2]
         self.G.batches.update(before[3])
         self.D.batches.update(before[4])
-        self.lam = before[5]
+        self.lam = self._lam_dev = before[5]
         self._dstate_host = (self.round, self.G.step, self.D.step)
         return g
 
@@ -873,6 +918,17 @@ class ConvGanStep:
         if want != self._dstate_host:
             self.dstate[:3].copy_(torch.tensor(want, dtype=torch.int32))
             self._dstate_host = want
+        if self._nv_stale and not self.short:     # (a ragged shard's sampler rewrites nv every round itself)
+            self.nv.fill_(self.B)
+            self._nv_stale = False
+        self._sync_lam()
+
+    def _sync_lam(self):
+        """The device lambda (rblk[0]) must hold the host's: rewritten only when the host moved without it
+        (construction with a loaded lambda, load_resume_state, a caller that set ``lam``)."""
+        if self.lam != self._lam_dev:
+            self.rblk[0:1].copy_(torch.tensor([self.lam], dtype=torch.float32))
+            self._lam_dev = self.lam
 
     def _capture(self, split=False):
         before = self._host_state()
@@ -894,7 +950,7 @@ class ConvGanStep:
         self.round, self.G.step, self.D.step = before[0], before[1], before[2]
         self.G.batches.update(before[3])
         self.D.batches.update(before[4])
-        self.lam = before[5]
+        self.lam = self._lam_dev = before[5]
         self._dstate_host = (self.round, self.G.step, self.D.step)
         self._graph_delta = ({k: after[3][k] - before[3][k] for k in before[3]},
                              {k: after[4][k] - before[4][k] for k in before[4]})
@@ -912,6 +968,7 @@ class ConvGanStep:
         self.G.step += 1
         self.D.step += 1
         self._lam_step()
+        self._lam_dev = self.lam
         self.round += 1
         self._dstate_host = (self.round, self.G.step, self.D.step)
 
@@ -921,6 +978,48 @@ class ConvGanStep:
         return {"round": self.round, "d_real": float(l[0]), "d_fake": float(l[1]),
                 "d_loss": float((l[0] + l[1]) * half), "g_loss": float(l[2]), "lambda": self.lam}
 
+    # ------------------------------------------------------------------ device round log
+    @property
+    def log_capacity(self):
+        """Rounds the device round log keeps (a ring: round r overwrites round r - log_capacity)."""
+        return C.lib.cgl_conv_round_log_capacity()
+
+    def losses_log(self, first: int, count: int):
+        """The scalars of rounds ``first`` .. ``first + count - 1`` (1-based, as ``stats()["round"]`` after each), one
+        dict per round, read from the device round log with one copy (two when the range wraps in the ring) and
+        one stream synchronise -- what the reference prints after every communication round (capgan.py:177-183),
+        also for the rounds inside a ``run_rounds`` launch.  Keys: ``round, d_real, d_fake, d_loss, g_loss, alpha,
+        F, lambda, real_rows, g_step, d_step``.  LookupError when a round of the range is not in the log (not run
+        yet, overwritten, or cleared by ``load_resume_state``); ValueError for a range no read can take."""
+        return self.log_dicts(self.read_log(first, count))
+
+    def read_log(self, first: int, count: int):
+        """The raw records (``_lib.ConvRoundRec`` array, a host copy of its own) of ``losses_log``'s range: the
+        device read without the conversion, for a caller that formats them later (``log_dicts``)."""
+        first, count = int(first), int(count)
+        cap = self.log_capacity
+        if first < 1 or count < 1 or count > cap:
+            raise ValueError(f"rounds {first}..{first + count - 1}: rounds are numbered from 1 and one read takes "
+                             f"1..{cap} of them (the round log's capacity)")
+        if self._log_host is None:     # page-locked: the copy goes straight to it, no staging
+            self._log_host = torch.empty(cap * ctypes.sizeof(C.ConvRoundRec), dtype=torch.uint8, pin_memory=True)
+        buf = (C.ConvRoundRec * count).from_address(self._log_host.data_ptr())
+        rc = C.lib.cgl_conv_read_round_log(ctypes_ptr(self.rlog), first, count, buf,
+                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc == -2:
+            raise LookupError(f"rounds {first}..{first + count - 1} are not all in the round log (capacity {cap} "
+                              "rounds: not run yet, overwritten, or cleared by a resume load)")
+        C.check(rc, "cgl_conv_read_round_log")
+        out = (C.ConvRoundRec * count)()
+        ctypes.memmove(out, buf, ctypes.sizeof(out))
+        return out
+
+    def log_dicts(self, recs):
+        """``read_log``'s records as ``losses_log``'s dicts."""
+        return [{"round": r.round, "d_real": r.d_real, "d_fake": r.d_fake, "d_loss": r.d_loss, "g_loss": r.g_loss,
+                 "alpha": r.alpha, "F": r.F, "lambda": r.lambda_, "real_rows": r.real_rows, "g_step": r.g_step,
+                 "d_step": r.d_step} for r in recs]
+
     def xd(self):
         return self.x3[self.B:2 * self.B]
 
@@ -929,5 +1028,4 @@ class ConvGanStep:
 
 
 def ctypes_ptr(t):
-    import ctypes
     return ctypes.c_void_p(t.data_ptr())

@@ -501,7 +501,7 @@ class ConvWorkerExchange:
         else:
             s.round_a(real, eager=eager)
             self.comm.all_gather(s.losses_all, s.lbuf[2:3])
-            O.weights_scale(s.weighting, s.lam, s.beta, s.losses_all, s.rank, s.dimg)
+            O.weights_scale(s.weighting, s.lam, s.beta, s.losses_all, s.rank, s.dimg, alpha_out=s.alpha_all)
             self.comm.all_reduce_sum(s.dimg)
             if (share or swap) and s.D.p.is_cuda:
                 # as WorkerExchange.round: phase B (G backward + Adam G) never touches D, so the D
@@ -548,7 +548,7 @@ class ConvLocalComm:
         losses = torch.cat([s.lbuf[2:3] for s in ss])
         for s in ss:
             s.losses_all.copy_(losses)
-            O.weights_scale(s.weighting, s.lam, s.beta, s.losses_all, s.rank, s.dimg)
+            O.weights_scale(s.weighting, s.lam, s.beta, s.losses_all, s.rank, s.dimg, alpha_out=s.alpha_all)
         tot = ss[0].dimg.clone()
         for s in ss[1:]:
             tot += s.dimg

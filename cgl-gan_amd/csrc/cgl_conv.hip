@@ -2835,18 +2835,99 @@ struct CglWgradReduceMulti {
   // the round's device counters (cgl_conv_wgrad_defer_counters), one extra last block when cnt != null:
   // *cnt_snap = cnt[cnt_si], then cnt[0 .. cnt_n) += cnt_v (nothing else in the launch reads them)
   int* cnt; int* cnt_snap; int cnt_n, cnt_v, cnt_si;
+  // the round's log record (cgl_conv_wgrad_defer_log), written by that same last block when lg.ring != null (the block
+  // exists for the record alone when cnt == null); lg.counters: where the block reads the round and step counts
+  // (== cnt when both are recorded), null: the host integers of lg
+  cgl_conv_round_log_args lg;
 };
+
+// The conv round's log record (cgl_conv_round_rec) and the device Lambda's step, by 16 lanes of one wave: every lane
+// computes the record (uniform loads, a few dozen flops) and lane l stores word l of slot (rnd - 1) % cap, lane 0 also
+// the advanced Lambda.  F as cgl_round_tail (cgl_kernels.hip) -- mean: sum_q l_q / N; else sum_q alpha_q l_q - 0.001f
+// lambda -- in rank order with every multiply-add written as fmaf and contraction off for the rest, so the deferred
+// launch and the separate one round identically; Lambda as ConvGanStep._lam_step (two fp32 roundings).  The callers
+// read rnd / gs / ds (the completed round, G steps, D steps) themselves: before their barrier where the same block
+// advances the counters.  Two halves, so that the deferred launch issues the record's loads together with its
+// counter reads (one memory round trip before the barrier) and only stores after it:
+// cgl_conv_log_word: lane l's word of the record (and the advanced Lambda); cgl_conv_log_store: the stores.
+__device__ __forceinline__ unsigned cgl_conv_log_word(const cgl_conv_round_log_args& a, int rnd, int gs, int ds, int lane,
+                                                      float& lam_out) {
+#pragma clang fp contract(off)
+  const int N = a.n_workers;
+  const float d_real = gld(a.lbuf), d_fake = gld(a.lbuf + 1), g = gld(a.lbuf + 2);
+  const float lam = gld(a.lam_dev);
+  const int nv = gldi(a.nv);
+  const bool mean = a.weighting == CGL_W_MEAN;
+  float s = 0.f, alpha = 1.f, F;
+  if (N == 1) {
+    s = g;                           // alpha = 1 exactly (capgan.py:247-248 with one worker)
+  } else {
+    for (int q = 0; q < N; ++q) {
+      const float lq = gld(a.losses_all + q);
+      s = mean ? s + lq : fmaf(gld(a.alpha_all + q), lq, s);
+    }
+    alpha = gld(a.alpha_all + a.rank);
+  }
+  F = mean ? s / N : fmaf(-0.001f, lam, s);
+  // optim.SGD([Lambda], lr=0.1) with dF/dLambda = -0.001 (capgan.py:249,259); MD-GAN's mean has no Lambda
+  const float lam_new = mean ? lam : lam + (-0.1f) * (-0.001f);
+  const float d_loss = (d_real + d_fake) * a.half;
+  unsigned w = 0u;
+  if (lane == 0) w = (unsigned)rnd;
+  else if (lane == 1) w = __float_as_uint(d_real);
+  else if (lane == 2) w = __float_as_uint(d_fake);
+  else if (lane == 3) w = __float_as_uint(d_loss);
+  else if (lane == 4) w = __float_as_uint(g);
+  else if (lane == 5) w = __float_as_uint(alpha);
+  else if (lane == 6) w = __float_as_uint(F);
+  else if (lane == 7) w = __float_as_uint(lam_new);
+  else if (lane == 8) w = (unsigned)nv;
+  else if (lane == 9) w = (unsigned)gs;
+  else if (lane == 10) w = (unsigned)ds;
+  lam_out = lam_new;
+  return w;
+}
+__device__ __forceinline__ void cgl_conv_log_store(const cgl_conv_round_log_args& a, int rnd, int lane, unsigned w,
+                                                   float lam_new) {
+  static_assert(sizeof(cgl_conv_round_rec) == 64, "cgl_conv_round_rec: one 64-byte line (ABI)");
+  cgl_gu32* rec = (cgl_gu32*)(a.ring + ((unsigned)(rnd - 1) % CGL_CONV_ROUND_LOG_CAP));
+  rec[lane] = w;
+  if (lane == 0) gst(a.lam_dev, lam_new);
+}
+
+__global__ __launch_bounds__(64) void cgl_conv_round_log_k(cgl_conv_round_log_args a) {
+  int rnd = a.round, gs = a.g_step, ds = a.d_step;
+  if (a.counters) { rnd = gldi(a.counters) + 1; gs = gldi(a.counters + 1) + 1; ds = gldi(a.counters + 2) + 1; }
+  if (threadIdx.x < 16) {
+    float lam_new;
+    const unsigned w = cgl_conv_log_word(a, rnd, gs, ds, (int)threadIdx.x, lam_new);
+    cgl_conv_log_store(a, rnd, (int)threadIdx.x, w, lam_new);
+  }
+}
 
 __global__ __launch_bounds__(256) void cgl_conv_wgrad_reduce_multi(CglWgradReduceMulti m) {
   __shared__ double red[256];
   const int b = blockIdx.x, n = m.n;
   const int fend = m.begin[n] + m.c1_blocks + m.fbeg[m.nfin];
-  if (b >= fend + m.d1_blocks) {     // the counters block
+  if (b >= fend + m.d1_blocks) {     // the counters / round-log block
     const int t = threadIdx.x;
-    const int snap = m.cnt[m.cnt_si];
-    __syncthreads();                 // (every lane has read the snapshot value before lane 0..n-1 add)
-    if (t == 0) *m.cnt_snap = snap;
-    if (t < m.cnt_n) m.cnt[t] += m.cnt_v;
+    int snap = 0, rnd = m.lg.round, gs = m.lg.g_step, ds = m.lg.d_step;
+    if (m.cnt) snap = m.cnt[m.cnt_si];
+    if (m.lg.ring && m.lg.counters) {     // (== cnt under the counters fold: read before the barrier and the add)
+      rnd = gldi(m.lg.counters) + 1; gs = gldi(m.lg.counters + 1) + 1; ds = gldi(m.lg.counters + 2) + 1;
+    }
+    // the record on 16 lanes of the second wave, off the counters lanes' chain (the launch's tail): its loads go out
+    // beside the counter reads, its stores after the barrier beside the add
+    const bool logl = m.lg.ring && t >= 64 && t < 80;
+    unsigned lw = 0u;
+    float lam_new = 0.f;
+    if (logl) lw = cgl_conv_log_word(m.lg, rnd, gs, ds, t - 64, lam_new);
+    __syncthreads();                 // (every lane has read the counters before lane 0..n-1 add)
+    if (m.cnt) {
+      if (t == 0) *m.cnt_snap = snap;
+      if (t < m.cnt_n) m.cnt[t] += m.cnt_v;
+    }
+    if (logl) cgl_conv_log_store(m.lg, rnd, t - 64, lw, lam_new);
     return;
   }
   if (b >= fend) {
@@ -4364,6 +4445,12 @@ int cgl_conv_wgrad_defer_begin(void) {
   return CGL_OK;
 }
 
+int cgl_conv_wgrad_defer_cancel(void) {
+  if (!t_wdefer.on) return CGL_E_STATE;
+  t_wdefer = WgradDefer{};
+  return CGL_OK;
+}
+
 int cgl_conv_wgrad_defer_counters(int* counters, int n, int v, int* snap, int snap_index) {
   if (!t_wdefer.on || t_wdefer.m.cnt) return CGL_E_STATE;
   if (!counters || !snap || n < 1 || n > 64 || snap_index < 0 || snap_index >= n) return CGL_E_ARG;
@@ -4372,12 +4459,64 @@ int cgl_conv_wgrad_defer_counters(int* counters, int n, int v, int* snap, int sn
   return CGL_OK;
 }
 
+static_assert(CGL_CONV_ROUND_LOG_CAP >= 4 * CGL_MAX_GRAPH_ROUNDS, "conv round log: several multi-round launches deep");
+
+static int conv_log_args_ok(const cgl_conv_round_log_args* a) {
+  if (!a || !a->ring || !a->lam_dev || !a->lbuf || !a->nv) return CGL_E_ARG;
+  if (a->weighting < 0 || a->weighting > 4 || a->n_workers < 1 || a->n_workers > CGL_MAX_WORKERS || a->rank < 0 ||
+      a->rank >= a->n_workers)
+    return CGL_E_ARG;
+  if (a->n_workers > 1 && (!a->losses_all || !a->alpha_all)) return CGL_E_ARG;
+  if (!a->counters && a->round < 1) return CGL_E_ARG;
+  return CGL_OK;
+}
+
+int cgl_conv_wgrad_defer_log(const cgl_conv_round_log_args* a) {
+  if (!t_wdefer.on || t_wdefer.m.lg.ring) return CGL_E_STATE;
+  if (const int rc = conv_log_args_ok(a)) return rc;
+  t_wdefer.m.lg = *a;
+  return CGL_OK;
+}
+
+int cgl_conv_round_log(const cgl_conv_round_log_args* a, void* stream) {
+  CGL_BATCH_GUARD();
+  if (const int rc = conv_log_args_ok(a)) return rc;
+  hipLaunchKernelGGL(cgl_conv_round_log_k, dim3(1), dim3(64), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+int cgl_conv_round_log_capacity(void) { return CGL_CONV_ROUND_LOG_CAP; }
+
+int cgl_conv_read_round_log(const cgl_conv_round_rec* ring_dev, int first_round, int count,
+                            cgl_conv_round_rec* out_host, void* stream) {
+  CGL_BATCH_GUARD();
+  if (!ring_dev || !out_host || first_round < 1 || count < 1 || count > CGL_CONV_ROUND_LOG_CAP) return CGL_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  // round r lives in slot (r - 1) % cap: one copy, or two when the range runs past the end of the ring
+  const int slot0 = (int)(((int64_t)first_round - 1) % CGL_CONV_ROUND_LOG_CAP);
+  const int n1 = std::min(count, CGL_CONV_ROUND_LOG_CAP - slot0);
+  hipError_t e = hipMemcpyAsync(out_host, ring_dev + slot0, (size_t)n1 * sizeof(cgl_conv_round_rec),
+                                hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && n1 < count)
+    e = hipMemcpyAsync(out_host + n1, ring_dev, (size_t)(count - n1) * sizeof(cgl_conv_round_rec),
+                       hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return (int)e;
+  for (int i = 0; i < count; ++i)
+    if ((int64_t)out_host[i].round != (int64_t)first_round + i) return CGL_E_STATE;   // never written / overwritten / cleared
+  return CGL_OK;
+}
+
 int cgl_conv_wgrad_defer_end(void* stream) {
   if (!t_wdefer.on) return CGL_E_STATE;
   t_wdefer.on = false;
   CglWgradReduceMulti& m = t_wdefer.m;
   if (!t_wdefer.has_c1) m.c1_blocks = 0;
-  const int blocks = m.begin[m.n] + m.c1_blocks + m.fbeg[m.nfin] + m.d1_blocks + (m.cnt ? 1 : 0);
+  if (m.lg.ring && m.cnt) {     // one block does both: it takes the round and step counts from the counters it advances
+    if ((m.lg.counters && m.lg.counters != m.cnt) || m.cnt_n < 3) return CGL_E_ARG;
+    m.lg.counters = m.cnt;
+  }
+  const int blocks = m.begin[m.n] + m.c1_blocks + m.fbeg[m.nfin] + m.d1_blocks + ((m.cnt || m.lg.ring) ? 1 : 0);
   if (blocks == 0) return CGL_OK;
   hipLaunchKernelGGL(cgl_conv_wgrad_reduce_multi, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
   return (int)hipGetLastError();

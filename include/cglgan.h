@@ -408,12 +408,80 @@ int cgl_conv_batch_end(void* stream);
  * Returns CGL_E_STATE for a nested begin or an end without begin. */
 int cgl_conv_wgrad_defer_begin(void);
 int cgl_conv_wgrad_defer_end(void* stream);
+/* Close an open deferral WITHOUT launching what it recorded (an error path: the pass that opened it failed half
+ * way, or a caller only probed the call-order rules).  The recorded reductions are dropped, so the gradients of
+ * that pass are incomplete.  CGL_E_STATE outside a deferral. */
+int cgl_conv_wgrad_defer_cancel(void);
 /* Inside an open deferral: the deferred launch also carries the round's device counters (one extra block, after
  * every other deferred step of the launch): *snap = counters[snap_index], then counters[0 .. n) += v, n <= 64 --
  * cgl_counters_add folded into the G backward's deferred launch of the conv round (its G Adam then reads the
  * completed-step count from *snap).  Nothing else in the launch may read the counters.  At most once per
  * deferral (CGL_E_STATE otherwise, or outside a deferral). */
 int cgl_conv_wgrad_defer_counters(int* counters, int n, int v, int* snap, int snap_index);
+
+/* ---- device round log of the conv round ------------------------------------------------------
+ * One completed conv round's scalars: what the reference prints after every communication round (F and Lambda,
+ * capgan.py:177-183) plus the losses behind them.  The conv ops have no context object, so the ring --
+ * CGL_CONV_ROUND_LOG_CAP records, 16 KB -- and the device lambda (one float) are plain device buffers of the caller
+ * (cglgan.conv_step.ConvGanStep owns them); round r lives in slot (r - 1) % CGL_CONV_ROUND_LOG_CAP, so the rounds
+ * of a multi-round graph stay readable one by one.  64 bytes (one line); the layout is part of the ABI. */
+#define CGL_CONV_ROUND_LOG_CAP 256
+typedef struct cgl_conv_round_rec {
+  int round;        /* 1-based number of the completed round (0: slot never written / cleared)                 */
+  float d_real;     /* the D step's loss on the real call ...                                                   */
+  float d_fake;     /* ... and on the fake call                                                                 */
+  float d_loss;     /* (d_real + d_fake) * half in fp32, in that order (half: 0.5 LSGAN, 1 BCE)                 */
+  float g_loss;     /* this worker's G loss                                                                     */
+  float alpha;      /* this worker's alpha (n_workers == 1: 1 exactly)                                          */
+  float F;          /* mean: sum_q l_q / N; else sum_q alpha_q l_q - 0.001f * lambda before the round (rank     */
+                    /* order, fp32, every multiply-add fused)                                                   */
+  float lambda_;    /* Lambda after the round: + (-0.1f) * (-0.001f) in fp32 (capgan.py:249,259), mean: unchanged */
+  int real_rows;    /* images of the D step's real call (the short final batch of a pass has fewer)             */
+  int g_step;       /* G / D Adam steps completed after the round                                               */
+  int d_step;
+  int reserved_[5];
+} cgl_conv_round_rec;
+/* The record's inputs.  lam_dev: the device Lambda (read, then advanced).  lbuf: d_real, d_fake, g_loss as the loss
+ * heads wrote them.  nv: the real call's image count.  n_workers > 1: losses_all[n_workers] (the gathered G losses)
+ * and alpha_all[n_workers] (cgl_weights_scale's alpha_out) are read too; with one worker they may be null.
+ * counters (may be null): device int32 {completed rounds, G Adam steps, D Adam steps} BEFORE this round's advance --
+ * the record takes round, g_step and d_step as each + 1; null: the host integers round, g_step, d_step (already
+ * counting this round) are recorded. */
+typedef struct cgl_conv_round_log_args {
+  cgl_conv_round_rec* ring;
+  float* lam_dev;
+  const float* lbuf;
+  const int* nv;
+  const float* losses_all;
+  const float* alpha_all;
+  const int* counters;
+  int n_workers, rank, weighting;
+  float half;
+  int round, g_step, d_step;
+} cgl_conv_round_log_args;
+/* Inside an open deferral: the deferred launch also writes the round's record and advances the device Lambda -- no
+ * launch is added.  The workgroup that does it is the counters block of cgl_conv_wgrad_defer_counters when both are
+ * recorded (one extra last block either way): it reads the round number and step counts before its barrier and
+ * before the add, from the deferral's own counters (a->counters must then be null or the same pointer; n >= 3), so
+ * no other block of the launch reads counters that one block is adding to.  Without the counters fold it reads
+ * a->counters (nothing in the launch writes them) or takes the host integers.  At most once per deferral
+ * (CGL_E_STATE otherwise, or outside a deferral); CGL_E_ARG for a null ring / lam_dev / lbuf / nv, a weighting
+ * outside CGL_WEIGHT_*, n_workers outside 1 .. 64, rank outside the workers, n_workers > 1 without losses_all and
+ * alpha_all, or counters that contradict the deferral's. */
+int cgl_conv_wgrad_defer_log(const cgl_conv_round_log_args* a);
+/* The same record from a one-workgroup launch of its own, for a round without a deferred launch (same argument
+ * rules; nothing else on the stream may be advancing a->counters between the round's kernels and this launch). */
+int cgl_conv_round_log(const cgl_conv_round_log_args* a, void* stream);
+/* Capacity of the ring in records (host only; CGL_CONV_ROUND_LOG_CAP, >= 4 * CGL_MAX_GRAPH_ROUNDS). */
+int cgl_conv_round_log_capacity(void);
+/* Copy the records of rounds first_round ... first_round + count - 1 from the ring at ring_dev to the host array
+ * out_host (count records): one asynchronous copy on `stream`, or two when the range wraps past the end of the ring,
+ * then one stream synchronise.  CGL_E_ARG: a null pointer, first_round < 1, count < 1 or count >
+ * CGL_CONV_ROUND_LOG_CAP (checked before any device access).  CGL_E_STATE: a copied record does not hold the round
+ * asked for (not run yet, overwritten by round + CGL_CONV_ROUND_LOG_CAP, or cleared); out_host is then unspecified. */
+int cgl_conv_read_round_log(const cgl_conv_round_rec* ring_dev, int first_round, int count,
+                            cgl_conv_round_rec* out_host, void* stream);
+
 int cgl_conv3x3_fwd_packed(const float* X, const float* Wp, const float* bias, float* Y, int n, int h, int w, int cin,
                            int cout, int stride, int up, int act, float slope, const float* drop, void* workspace,
                            int64_t ws_bytes, void* stream);
