@@ -36,6 +36,7 @@ EXPORTS = [
     "cgl_nchw_to_nhwc", "cgl_nhwc_to_nchw", "cgl_dense1_bwd_data_nhwc", "cgl_dense1_fwd_nhwc", "cgl_dense1_head_nhwc", "cgl_adv_loss", "cgl_adam_multi", "cgl_dense_workspace_bytes",
     "cgl_dense_fwd", "cgl_dense_bwd_data", "cgl_dense_bwd_weight", "cgl_gather_rows", "cgl_weights_scale",
     "cgl_conv_packed_floats", "cgl_conv_pack_multi", "cgl_conv_batch_begin", "cgl_conv_batch_end", "cgl_conv_wgrad_defer_begin", "cgl_conv_wgrad_defer_end", "cgl_conv_wgrad_defer_counters", "cgl_conv3x3_bias_by_colsum",
+    "cgl_conv_set_mma_dtype", "cgl_conv_get_mma_dtype",
     "cgl_conv_wgrad_defer_cancel", "cgl_conv_wgrad_defer_log", "cgl_conv_round_log", "cgl_conv_round_log_capacity", "cgl_conv_read_round_log", "cgl_conv3x3_fwd_packed", "cgl_conv3x3_bwd_data_packed",
     "cgl_dense_fwd_packed", "cgl_dense_bwd_data_packed", "cgl_conv3x3_stat_chunks", "cgl_conv3x3_fwd_packed_stats",
     "cgl_bn2d_fwd_stats", "cgl_bn2d_fwd_stats_coef", "cgl_conv3x3_fwd_packed_bnin", "cgl_bn2d_stats_scratch_bytes", "cgl_linear_desc_bytes", "cgl_linear_prepare", "cgl_linear_prepare_gather", "cgl_linear_prepare_wgrad_nhwc",
@@ -211,6 +212,8 @@ def _load():
         "cgl_conv_batch_begin": (ci, [vp]),
         "cgl_conv_batch_end": (ci, [vp]),
         "cgl_conv3x3_bias_by_colsum": (ci, [ci, ci, ci, ci, ci, ci, ci]),
+        "cgl_conv_set_mma_dtype": (ci, [ci]),
+        "cgl_conv_get_mma_dtype": (ci, []),
         "cgl_conv_wgrad_defer_begin": (ci, []),
         "cgl_conv_wgrad_defer_end": (ci, [vp]),
         "cgl_conv_wgrad_defer_counters": (ci, [vp, ci, ci, vp, ci]),

@@ -78,6 +78,38 @@ def wgrad_defer(enabled=True):
             C.check(rc, "cgl_conv_wgrad_defer_end")
 
 
+MMA_DTYPES = {"f32": C.DTYPE_F32, "bf16": C.DTYPE_BF16}
+
+
+def _mma_dtype_code(dt):
+    if isinstance(dt, str):
+        if dt not in MMA_DTYPES:
+            raise ValueError(f"conv MFMA operand type {dt!r}: expected 'f32' or 'bf16' (f16 would need loss "
+                             "scaling, which the conv path does not have)")
+        return MMA_DTYPES[dt]
+    return int(dt)
+
+
+def get_mma_dtype() -> int:
+    """The calling thread's MFMA operand type for the conv3x3 ops (C.DTYPE_F32 / C.DTYPE_BF16)."""
+    return C.lib.cgl_conv_get_mma_dtype()
+
+
+@contextlib.contextmanager
+def mma_dtype(dt):
+    """cgl_conv_set_mma_dtype for the block: ``"f32"`` / ``"bf16"`` (or C.DTYPE_*) is the operand type of the MFMA
+    convolution kernels for every conv3x3 op issued inside (vector-kernel layers and the dense ops stay fp32); the
+    previous mode is restored on exit, also when the block raises.  Must be entered and left outside a
+    launch_batch / wgrad_defer block."""
+    code = _mma_dtype_code(dt)
+    prev = C.lib.cgl_conv_get_mma_dtype()
+    C.check(C.lib.cgl_conv_set_mma_dtype(code), "cgl_conv_set_mma_dtype")
+    try:
+        yield
+    finally:
+        C.lib.cgl_conv_set_mma_dtype(prev)
+
+
 @contextlib.contextmanager
 def stream_cache():
     """Resolve the current torch stream once for a block of ops that all run on it (the fused conv

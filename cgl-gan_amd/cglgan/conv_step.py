@@ -144,9 +144,19 @@ class ConvGanStep:
     """Fused CAPGAN worker round of the model/lsgan.py GAN (see module docstring)."""
 
     def __init__(self, batch, loss="mse", data=None, seed=20211212, n_workers=1, rank=0, weighting="capgan",
-                 lr=2e-4, betas=(0.5, 0.999), adam_eps=1e-8, gen_z=True, beta=None, device="cuda", graph=False):
+                 lr=2e-4, betas=(0.5, 0.999), adam_eps=1e-8, gen_z=True, beta=None, device="cuda", graph=False,
+                 gemm_dtype="f32"):
         if loss not in ("mse", "bce"):
             raise ValueError("loss must be 'mse' (LSGAN) or 'bce' (Sigmoid + BCELoss)")
+        # operand type of the MFMA convolution kernels (conv_ops.mma_dtype; accumulation stays fp32; the
+        # Conv2d(64, 1) / Conv2d(1, 16) vector kernels and both Linears stay fp32).  A constructor argument, not
+        # state: resume_state() does not carry it
+        if gemm_dtype == "f16":
+            raise ValueError("gemm_dtype='f16': the conv round has no loss scaling (f16's exponent range needs the "
+                             "scaler / skip-step machinery of the MLP step); use 'bf16' or 'f32'")
+        if gemm_dtype not in O.MMA_DTYPES:
+            raise ValueError("gemm_dtype must be 'f32' or 'bf16'")
+        self.gemm_dtype = gemm_dtype
         if batch < 2:
             raise ValueError("BatchNorm in train mode needs batch >= 2")
         dev = torch.device(device)
@@ -724,7 +734,9 @@ class ConvGanStep:
     def phase_a(self, real=None):
         """G forward (Xd, Xg), the local D step, the G loss through the updated D and its gradient
         w.r.t. Xg (capgan.py:215-225, 322-347).  Ends with ``dimg`` = d l_rank / d Xg."""
-        with O.stream_cache():     # every op of the phase runs on the current stream
+        # every op of the phase runs on the current stream, with this step's MFMA operand type (the thread's mode
+        # is restored on exit; a captured phase keeps the kernels of the type it was captured with)
+        with O.mma_dtype(self.gemm_dtype), O.stream_cache():
             self._phase_a(real)
 
     def _round_start(self, real):
@@ -793,7 +805,7 @@ class ConvGanStep:
     def phase_b(self):
         """Replicated G backward from the (exchanged) image gradient, lambda SGD, Adam G (capgan.py:258-260)."""
         fold = self.graph and self.wdefer and self.cnt_fold
-        with O.stream_cache():
+        with O.mma_dtype(self.gemm_dtype), O.stream_cache():
             self._g_backward(counters=fold)
             self.G.adam(self.lr, self.betas, self.eps,
                         step_dev=(self.dstate[4:5] if fold else self.dstate[1:2]) if self.graph else None)
@@ -976,7 +988,8 @@ class ConvGanStep:
         l = self.lbuf.cpu()
         half = 0.5 if self.loss == "mse" else 1.0
         return {"round": self.round, "d_real": float(l[0]), "d_fake": float(l[1]),
-                "d_loss": float((l[0] + l[1]) * half), "g_loss": float(l[2]), "lambda": self.lam}
+                "d_loss": float((l[0] + l[1]) * half), "g_loss": float(l[2]), "lambda": self.lam,
+                "gemm_dtype": self.gemm_dtype}
 
     # ------------------------------------------------------------------ device round log
     @property

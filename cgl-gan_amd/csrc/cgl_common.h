@@ -13,6 +13,29 @@ bool cgl_launch_batch_open();
   } while (0)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// 16-bit operand MFMAs (the MLP GEMMs: cgl_gan_config.gemm_dtype, BASELINE config 5; the conv kernels:
+// cgl_conv_set_mma_dtype): the fp32 operands are rounded to fp16 / bf16 (round-to-nearest-even) as
+// they enter the MFMA; products are exact and accumulate in fp32.  The k-permuted fragment of a 16-k
+// chunk (lane half h holds k = 8h .. 8h + 7) is exactly the operand of
+// v_mfma_f32_32x32x16_{f16,bf16}, so one MFMA replaces the eight 32x32x2 f32 MFMAs of the chunk.
+template <int DT>
+__device__ __forceinline__ void cgl_mfma16(f32x16& acc, const float (&a)[8], const float (&b)[8]) {
+  if constexpr (DT == CGL_DTYPE_F16) {
+    f16x8 x, y;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { x[q] = (_Float16)a[q]; y[q] = (_Float16)b[q]; }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, acc, 0, 0, 0);
+  } else {
+    bf16x8 x, y;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { x[q] = (__bf16)a[q]; y[q] = (__bf16)b[q]; }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc, 0, 0, 0);
+  }
+}
+
 typedef CGL_GLOBAL unsigned int cgl_gu32;
 typedef CGL_GLOBAL unsigned long long cgl_gu64;
 __device__ __forceinline__ void cgl_pub2f(float* p, float a, float b) {

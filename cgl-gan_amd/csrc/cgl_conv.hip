@@ -32,7 +32,12 @@
 //  * Every launch takes its descriptor by value (kernel arguments): no uploads, no host syncs, so
 //    the ops are stream-ordered and capturable in a hipGraph.
 //
-// Compiled in cgl_conv_tu.hip (shares cgl_internal.h / cgl_common.h: cgl_philox, cgl_lerp, ...).
+//  * The four MFMA kernel families (cgl_conv_fwd, cgl_conv_fwd_halo, cgl_conv_wgrad, cgl_conv_wgrad_lds) take
+//    their operand type at compile time: fp32 (above) or bf16 (cgl_conv_set_mma_dtype: the same fragments rounded
+//    as they enter one v_mfma_f32_32x32x16_bf16 per 16-k chunk, fp32 accumulation).
+//
+// Compiled in cgl_conv_tu.hip (shares cgl_internal.h / cgl_common.h: cgl_philox, cgl_lerp, ...); the bf16
+// instances of the MFMA kernels in cgl_conv_bf16.hip, which includes this file's kernel section only.
 
 #define CGL_CONV_MAXP 4
 #define CGL_AS4 __attribute__((address_space(4)))
@@ -147,9 +152,22 @@ __device__ __forceinline__ float cgl_bnin_slope(CglKL L) {
 #ifndef CGL_HALO_SB
 #define CGL_HALO_SB 8   // the halo window's staging loads in flight per thread (1: one load, then its store)
 #endif
-template <int TM, int TN, bool FAST, bool BNIN = false, bool HALO = false, bool LDSM = false>
+// DT (compile time, CGL_DTYPE_F32 / CGL_DTYPE_BF16; cgl_conv_set_mma_dtype): with bf16 the finished fragment of
+// a 16-k chunk -- after the masks and the folded BatchNorm -- is rounded to bf16 (RNE) and one
+// v_mfma_f32_32x32x16_bf16 replaces the chunk's eight f32 MFMAs (cgl_mfma16); loads, LDS staging (fp32),
+// accumulators and the epilogue are the fp32 kernel's.
+template <int DT, int TM, int TN>
+__device__ __forceinline__ void cgl_conv_mm16(f32x16 (&acc)[TM][TN], const float (&A)[TM][8], const float (&B)[TN][8]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) cgl_mfma16<DT>(acc[i][j], A[i], B[j]);
+}
+
+template <int TM, int TN, bool FAST, bool BNIN = false, bool HALO = false, bool LDSM = false, int DT = CGL_DTYPE_F32>
 __device__ __forceinline__ void cgl_conv_fwd_body(CglKL L, CglKP P, int local, float* s_red, bool direct = false) {
   constexpr int S = 3;
+  static_assert(DT == CGL_DTYPE_F32 || DT == CGL_DTYPE_BF16, "fp32 or bf16 MFMA operands");
   static_assert(!LDSM || (TM == 2 && TN == 2 && FAST && !BNIN && !HALO), "the LDS main loop: 2x2 blocks, FAST");
   static_assert(!BNIN || FAST, "the folded BatchNorm input needs the FAST (uniform-tap chunk) path");
   static_assert(!HALO || (TM == 2 && TN == 2 && FAST), "the halo path is the 2x2-block FAST path");
@@ -281,6 +299,10 @@ __device__ __forceinline__ void cgl_conv_fwd_body(CglKL L, CglKP P, int local, f
         for (int q = 0; q < 8; ++q) A[i][q] = ((okm >> (i * 8 + q)) & 1) ? A[i][q] : 0.f;
       }
     }
+    if constexpr (DT != CGL_DTYPE_F32) {
+      cgl_conv_mm16<DT>(acc, A, B);
+      return;
+    }
 #pragma unroll
     for (int q = 0; q < 8; ++q)
 #pragma unroll
@@ -361,6 +383,10 @@ __device__ __forceinline__ void cgl_conv_fwd_body(CglKL L, CglKP P, int local, f
         B[j][4] = v[0]; B[j][5] = v[1]; B[j][6] = v[2]; B[j][7] = v[3];
       }
       __builtin_amdgcn_sched_barrier(0);   // all 8 LDS reads ahead of the 32 MFMAs
+      if constexpr (DT != CGL_DTYPE_F32) {
+        cgl_conv_mm16<DT>(acc, A, B);
+        return;
+      }
 #pragma unroll
       for (int q = 0; q < 8; ++q)
 #pragma unroll
@@ -479,6 +505,10 @@ __device__ __forceinline__ void cgl_conv_fwd_body(CglKL L, CglKP P, int local, f
       }
     };
     auto mm = [&](float (&A)[TM][8], float (&B)[TN][8]) {
+      if constexpr (DT != CGL_DTYPE_F32) {
+        cgl_conv_mm16<DT>(acc, A, B);
+        return;
+      }
 #pragma unroll
       for (int q = 0; q < 8; ++q)
 #pragma unroll
@@ -745,7 +775,7 @@ __device__ __forceinline__ void cgl_conv_fwd_body(CglKL L, CglKP P, int local, f
   }
 }
 
-template <int TM, int TN, bool FAST, bool BNIN = false, bool LDSM = false>
+template <int TM, int TN, bool FAST, bool BNIN = false, bool LDSM = false, int DT = CGL_DTYPE_F32>
 __global__ __launch_bounds__(256) void cgl_conv_fwd(CglConvLaunch args) {
   (void)args;
   extern __shared__ float cgl_conv_lds[];
@@ -757,18 +787,18 @@ __global__ __launch_bounds__(256) void cgl_conv_fwd(CglConvLaunch args) {
     // units XCD-contiguous, so the np tiles reading one input window run back to back in one L2
     const int np = L->np;
     const int unit = cgl_xcd_tile(bid, L->p[0].tiles_m * L->p[0].tiles_n * np);
-    cgl_conv_fwd_body<TM, TN, FAST, BNIN, false, LDSM>(L, &L->p[unit % np], unit / np, cgl_conv_lds, true);
+    cgl_conv_fwd_body<TM, TN, FAST, BNIN, false, LDSM, DT>(L, &L->p[unit % np], unit / np, cgl_conv_lds, true);
     return;
   }
   const int pi = cgl_conv_prob(L, bid);
   CglKP P = &L->p[pi];
-  cgl_conv_fwd_body<TM, TN, FAST, BNIN, false, LDSM>(L, P, bid - P->wg_begin, cgl_conv_lds);
+  cgl_conv_fwd_body<TM, TN, FAST, BNIN, false, LDSM, DT>(L, P, bid - P->wg_begin, cgl_conv_lds);
 }
 
 // The phase-form upsampling conv with its input window staged in LDS (HALO path of cgl_conv_fwd_body): one
 // workgroup per (64-row tile, 64-output-channel slice), its 4 waves = the 4 output-parity problems
 // (launch_conv_mma: conv_halo_ok).
-template <bool BNIN>
+template <bool BNIN, int DT = CGL_DTYPE_F32>
 __global__ __launch_bounds__(256) void cgl_conv_fwd_halo(CglConvLaunch args) {
   (void)args;
   extern __shared__ float cgl_conv_lds[];
@@ -777,8 +807,8 @@ __global__ __launch_bounds__(256) void cgl_conv_fwd_halo(CglConvLaunch args) {
   // XCD-contiguous tile order: the N-halves of one row tile and vertically adjacent tiles (which share
   // window rows) run on one XCD's L2
   CglKP P = &L->p[wave];
-  cgl_conv_fwd_body<2, 2, true, BNIN, true>(L, P, cgl_xcd_tile(blockIdx.x, P->tiles_m * P->tiles_n), cgl_conv_lds,
-                                             true);
+  cgl_conv_fwd_body<2, 2, true, BNIN, true, false, DT>(L, P, cgl_xcd_tile(blockIdx.x, P->tiles_m * P->tiles_n),
+                                                        cgl_conv_lds, true);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -795,14 +825,16 @@ __global__ __launch_bounds__(256) void cgl_conv_fwd_halo(CglConvLaunch args) {
 // loads index it with an output channel (< N) or an input channel (< Cin), so it covers
 // CGL_ZERO_PAGE floats; conv_bwd_weight_impl refuses larger layers (dense layers reach N = 8192).
 #define CGL_ZERO_PAGE 65536
-__device__ float cgl_zero_page[CGL_ZERO_PAGE];
+static __device__ float cgl_zero_page[CGL_ZERO_PAGE];   // (one per translation unit that holds these kernels)
 
 // ROW: every problem of the launch has OW % 8 == 0 and M % 16 == 0, so the 8 pixels of a lane
 // half are always valid and lie in one output row: one pixel decode per chunk, constant address
 // strides along the row, the tap's row bounds checked once (a fraction of the generic path's VALU).
 // BNIN: X is the PRE-BatchNorm map (groups of L->in_gimg images, scale / shift in L->in_coef): each valid
 // im2col value is fmaf(x, scale, shift) (+ LeakyReLU), cgl_eltwise's arithmetic; padded taps stay zero
-template <int TM, int TN, bool ROW, bool BNIN = false>
+// DT: as in cgl_conv_fwd_body -- the finished dY / im2col fragments (the BatchNorm applied, the bias column's ones
+// set) are rounded to bf16 as they enter the MFMA, so the bias column sums the ROUNDED dY
+template <int TM, int TN, bool ROW, bool BNIN = false, int DT = CGL_DTYPE_F32>
 __device__ __forceinline__ void cgl_conv_wgrad_body(CglKL L, CglKP P, int local) {
 #ifndef CGL_WGRAD_S
 #define CGL_WGRAD_S 2
@@ -947,6 +979,10 @@ __device__ __forceinline__ void cgl_conv_wgrad_body(CglKL L, CglKP P, int local)
   };
   auto compute = [&](float (&A)[TM][8], float (&B)[TN][8], int okm) {
     (void)okm;
+    if constexpr (DT != CGL_DTYPE_F32) {
+      cgl_conv_mm16<DT>(acc, A, B);
+      return;
+    }
 #pragma unroll
     for (int q = 0; q < 8; ++q)
 #pragma unroll
@@ -992,14 +1028,14 @@ __device__ __forceinline__ void cgl_conv_wgrad_body(CglKL L, CglKP P, int local)
   }
 }
 
-template <int TM, int TN, bool ROW = false, bool BNIN = false>
+template <int TM, int TN, bool ROW = false, bool BNIN = false, int DT = CGL_DTYPE_F32>
 __global__ __launch_bounds__(256) void cgl_conv_wgrad(CglConvLaunch args) {
   (void)args;
   CglKL L = cgl_conv_args();
   const int bid = blockIdx.x;
   const int pi = cgl_conv_prob(L, bid);
   CglKP P = &L->p[pi];
-  cgl_conv_wgrad_body<TM, TN, ROW, BNIN>(L, P, bid - P->wg_begin);
+  cgl_conv_wgrad_body<TM, TN, ROW, BNIN, DT>(L, P, bid - P->wg_begin);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1019,10 +1055,12 @@ __global__ __launch_bounds__(256) void cgl_conv_wgrad(CglConvLaunch args) {
 #define CGL_WLDS_PAD 4
 // BNIN: X is the PRE-BatchNorm map of one forward call (group L->in_g0): the staged im2col values are
 // LeakyReLU(fmaf(x, scale, shift)) -- cgl_eltwise's arithmetic, so the panel equals the applied activation
-template <int WM, int WN, int KS, bool BNIN = false>
+// DT: the panels stay fp32 in LDS; a lane's 8 pixels of each panel column are rounded to bf16 as they enter the MFMA
+template <int WM, int WN, int KS, bool BNIN = false, int DT = CGL_DTYPE_F32>
 __global__ __launch_bounds__(256 * KS, 2 / KS) void cgl_conv_wgrad_lds(CglConvLaunch args) {
   (void)args;
   static_assert(KS == 1 || KS == 2, "one or two halves");
+  static_assert(DT == CGL_DTYPE_F32 || DT == CGL_DTYPE_BF16, "fp32 or bf16 MFMA operands");
   constexpr int R = 64 * WM, C = 64 * WN;
   constexpr int RP = R + CGL_WLDS_PAD, CP = C + CGL_WLDS_PAD;   // padded rows: the lane halves (8 rows
                                                                  // apart) land on disjoint banks
@@ -1131,6 +1169,19 @@ __global__ __launch_bounds__(256 * KS, 2 / KS) void cgl_conv_wgrad_lds(CglConvLa
   auto compute = [&](int buf) {
     const float* A = &sa0[buf * 16 * RP + 8 * lhf * RP + wm * 64 + li];
     const float* B = &sb0[buf * 16 * CP + 8 * lhf * CP + wn * 64 + li];
+    if constexpr (DT != CGL_DTYPE_F32) {
+      float a[2][8], b[2][8];   // [block][pixel q of this lane half]: the 16-bit MFMA's fragment
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        a[0][q] = A[q * RP];
+        a[1][q] = A[q * RP + 32];
+        b[0][q] = B[q * CP];
+        b[1][q] = B[q * CP + 32];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      cgl_conv_mm16<DT>(acc, a, b);
+      return;
+    }
     float a[8][2], b[8][2];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -1211,6 +1262,18 @@ __global__ __launch_bounds__(256 * KS, 2 / KS) void cgl_conv_wgrad_lds(CglConvLa
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// The bf16 instantiations of the four MFMA kernel families above (cgl_conv_set_mma_dtype) are compiled in a
+// translation unit of their own, cgl_conv_bf16.hip, which includes this file up to here and defines these launchers:
+// the same template arguments, grids and LDS sizes the fp32 dispatchers (launch_conv_mma, conv_bwd_weight_impl)
+// pass.  Each returns hipGetLastError(), or CGL_E_ARG for a combination the fp32 dispatchers never form.
+int cgl_conv_fwd_bf16(int tm, int tn, bool fast, bool bnin, bool ldsm, int wg, int lds, hipStream_t s,
+                      const CglConvLaunch& L);
+int cgl_conv_fwd_halo_bf16(bool bnin, int grid, int lds, hipStream_t s, const CglConvLaunch& L);
+int cgl_conv_wgrad_bf16(int tm, int tn, bool row, bool bnin, int wg, hipStream_t s, const CglConvLaunch& L);
+int cgl_conv_wgrad_lds_bf16(int wm, int ks, bool bnin, int wgl, hipStream_t s, const CglConvLaunch& L);
+
+#ifndef CGL_CONV_MMA_KERNELS_ONLY
 // ------------------------------------------------------------------------------------------
 // One-output-channel convolution on the vector ALUs (N == 1: Conv2d(64, 1) of the generator's
 // last layer, and the input gradient of the discriminator's Conv2d(1, 16)) -- an MFMA tile would
@@ -3465,6 +3528,10 @@ __global__ __launch_bounds__(256) void cgl_weights_scale_k(CglWeightsArgs a) {
 // Host side: tap tables, launch planning, C ABI.
 namespace {
 
+// cgl_conv_set_mma_dtype: the calling thread's operand type for the MFMA convolution kernels, read when a
+// cgl_conv3x3_* call is issued (so a stream capture records the kernels of the type then in force)
+thread_local int t_mma_dtype = CGL_DTYPE_F32;
+
 struct ConvGeom {
   int n, h, w, cin, cout, stride, up, ks;   // ks: kernel size 3 (padding 1) or 1 (dense layer)
   int hv, wv, ho, wo;        // virtual (upsampled) input dims, output dims
@@ -3787,8 +3854,9 @@ bool conv_halo_ok(const CglConvProb* P, int np) {
 
 int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float slope, const float* drop,
                     hipStream_t s, double* st_part = nullptr, int st_cpg = 0, const StatBwd* sb = nullptr,
-                    const BnIn* bi = nullptr, const int* st_nv = nullptr) {
+                    const BnIn* bi = nullptr, const int* st_nv = nullptr, int dt = CGL_DTYPE_F32) {
   const int N = P[0].N;
+  const bool bf16 = dt == CGL_DTYPE_BF16;   // the MFMA kernels' operand type (the vector kernels below ignore it)
   CglConvLaunch L;
   std::memset(&L, 0, sizeof(L));
   L.np = np;
@@ -3862,6 +3930,7 @@ int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float sl
       L.p[i] = P[i];
     }
     const int grid = P[0].M / 64 * (N / 64);
+    if (bf16) return cgl_conv_fwd_halo_bf16(L.in_coef != nullptr, grid, lds, s, L);
     if (L.in_coef) hipLaunchKernelGGL((cgl_conv_fwd_halo<true>), dim3(grid), dim3(256), lds, s, L);
     else hipLaunchKernelGGL((cgl_conv_fwd_halo<false>), dim3(grid), dim3(256), lds, s, L);
     return (int)hipGetLastError();
@@ -3892,6 +3961,7 @@ int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float sl
     for (int i = 0; i < np; ++i)
       if (P[i].Cin != P[0].Cin || P[i].Cin > 512) return CGL_E_ARG;
     if (!fast) return CGL_E_ARG;
+    if (bf16) return cgl_conv_fwd_bf16(t.TM, t.TM == 2 ? t.TN : 1, true, true, false, wg, lds, s, L);
     if (t.TM == 2 && t.TN == 2) hipLaunchKernelGGL((cgl_conv_fwd<2, 2, true, true>), dim3(wg), dim3(256), lds, s, L);
     else if (t.TM == 2) hipLaunchKernelGGL((cgl_conv_fwd<2, 1, true, true>), dim3(wg), dim3(256), lds, s, L);
     else hipLaunchKernelGGL((cgl_conv_fwd<1, 1, true, true>), dim3(wg), dim3(256), lds, s, L);
@@ -3900,7 +3970,10 @@ int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float sl
   // the 2 x 2-wave 128 x 128 tiling of a FAST problem: LDS-staged operand panels (CGL_CONV_LDSM=0: the direct
   // loads; bitwise the same results)
   const int ldsm_env = getenv("CGL_CONV_LDSM") ? atoi(getenv("CGL_CONV_LDSM")) : 1;   // (per launch: tests toggle it)
-  if (t.TM == 2 && t.TN == 2 && fast && ldsm_env && t.WM == 2 && t.WN == 2 && t.WK == 1) {
+  const bool ldsm = t.TM == 2 && t.TN == 2 && fast && ldsm_env && t.WM == 2 && t.WN == 2 && t.WK == 1;
+  if (bf16)
+    return cgl_conv_fwd_bf16(t.TM, t.TM == 2 ? t.TN : 1, fast, false, ldsm, wg, ldsm ? 2 * 2 * 128 * 20 * 4 : lds, s, L);
+  if (ldsm) {
     hipLaunchKernelGGL((cgl_conv_fwd<2, 2, true, false, true>), dim3(wg), dim3(256), 2 * 2 * 128 * 20 * 4, s, L);
   } else if (t.TM == 2 && t.TN == 2) {
     if (fast) hipLaunchKernelGGL((cgl_conv_fwd<2, 2, true>), dim3(wg), dim3(256), lds, s, L);
@@ -3991,6 +4064,9 @@ bool c1_ok(const ConvGeom& g) {
   return g.cin == 1 && g.ks == 3 && !g.up && g.cout % 4 == 0 && g.cout <= 16 && 256 % g.cout == 0;
 }
 
+// the 3x3 convolutions take the thread's MFMA operand type; the dense layers (ks = 1: cgl_dense_*) stay fp32
+int conv_mma_dtype(const ConvGeom& g) { return g.ks == 3 ? t_mma_dtype : CGL_DTYPE_F32; }
+
 int conv_fwd_impl(const ConvGeom& g, const float* X, const float* W, const float* bias, float* Y, int act, float slope,
                   const float* drop, void* ws, int64_t wsb, hipStream_t s, const float* Wp = nullptr,
                   double* st_part = nullptr, int st_groups = 1, const BnIn* bi = nullptr, const int* st_nv = nullptr) {
@@ -4031,7 +4107,7 @@ int conv_fwd_impl(const ConvGeom& g, const float* X, const float* W, const float
   int rc;
   if (Wp) pack_layout(P, np, Wp);
   else if ((rc = launch_pack(W, g, 0, P, np, (float*)ws, s))) return rc;
-  return launch_conv_mma(P, np, bias, act, slope, drop, s, st_part, cpg, nullptr, bi, st_nv);
+  return launch_conv_mma(P, np, bias, act, slope, drop, s, st_part, cpg, nullptr, bi, st_nv, conv_mma_dtype(g));
 }
 
 int conv_bwd_data_impl(const ConvGeom& g, const float* dY, const float* W, float* dX, void* ws, int64_t wsb,
@@ -4067,7 +4143,8 @@ int conv_bwd_data_impl(const ConvGeom& g, const float* dY, const float* W, float
   int rc;
   if (Wp) pack_layout(P, np, Wp);
   else if ((rc = launch_pack(W, g, 1, P, np, (float*)ws, s))) return rc;
-  return launch_conv_mma(P, np, nullptr, CGL_EPI_ACT_NONE, 0.f, nullptr, s, st_part, cpg, st_part ? sb : nullptr);
+  return launch_conv_mma(P, np, nullptr, CGL_EPI_ACT_NONE, 0.f, nullptr, s, st_part, cpg, st_part ? sb : nullptr, nullptr,
+                         nullptr, conv_mma_dtype(g));
 }
 
 // the ROW fast path of cgl_conv_wgrad_body: whole 8-pixel row segments in every problem
@@ -4143,6 +4220,8 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
     hipLaunchKernelGGL(cgl_conv_c1_wgrad_fin, dim3(g.cout * 10), dim3(256), 0, s, a);
     return (int)hipGetLastError();
   }
+  const bool bf16 = conv_mma_dtype(g) == CGL_DTYPE_BF16;   // the MFMA kernels' operand type (vector kernels: fp32)
+  int rc = 0;
   WgradPlan pl = wgrad_plan(g, db != nullptr);
   const bool bias_col = db && wgrad_bias_col(g, pl.P, pl.np);
   CglConvLaunch L;
@@ -4207,7 +4286,9 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
       P.wg_begin = wgl;
       wgl += P.tiles_m * P.tiles_n * P.splits;
     }
-    if (bi) {
+    if (bf16) {
+      if ((rc = cgl_conv_wgrad_lds_bf16(lwm, bi ? 1 : ks, bi != nullptr, wgl, s, L))) return rc;
+    } else if (bi) {
       if (lwm == 2) hipLaunchKernelGGL((cgl_conv_wgrad_lds<2, 2, 1, true>), dim3(wgl), dim3(256), 0, s, L);
       else hipLaunchKernelGGL((cgl_conv_wgrad_lds<1, 4, 1, true>), dim3(wgl), dim3(256), 0, s, L);
     } else if (ks == 2) {
@@ -4224,7 +4305,9 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
   else if (bi && !valu) {
     // the wave-unit MFMA weight gradient with the BatchNorm applied per loaded value (up to two groups)
     if (bi->groups - bi->g0 > 2 && bi->gimg < g.n) return CGL_E_ARG;
-    if (wgrad_row_ok(pl)) {
+    if (bf16) {
+      if ((rc = cgl_conv_wgrad_bf16(pl.t.TM, pl.t.TN, wgrad_row_ok(pl), true, wg, s, L))) return rc;
+    } else if (wgrad_row_ok(pl)) {
       if (pl.t.TM == 2 && pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 2, true, true>), dim3(wg), dim3(256), 0, s, L);
       else if (pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<1, 2, true, true>), dim3(wg), dim3(256), 0, s, L);
       else if (pl.t.TM == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 1, true, true>), dim3(wg), dim3(256), 0, s, L);
@@ -4257,6 +4340,9 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
   }
   else if (valu)
     hipLaunchKernelGGL(cgl_conv_wgrad_n1, dim3((pl.P[0].K + 255) / 256, pl.P[0].splits), dim3(256), 0, s, L);
+  else if (bf16) {
+    if ((rc = cgl_conv_wgrad_bf16(pl.t.TM, pl.t.TN, wgrad_row_ok(pl), false, wg, s, L))) return rc;
+  }
   else if (wgrad_row_ok(pl)) {
     if (pl.t.TM == 2 && pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 2, true>), dim3(wg), dim3(256), 0, s, L);
     else if (pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<1, 2, true>), dim3(wg), dim3(256), 0, s, L);
@@ -4267,7 +4353,6 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
   else if (pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<1, 2>), dim3(wg), dim3(256), 0, s, L);
   else if (pl.t.TM == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 1>), dim3(wg), dim3(256), 0, s, L);
   else hipLaunchKernelGGL((cgl_conv_wgrad<1, 1>), dim3(wg), dim3(256), 0, s, L);
-  int rc;
   if ((rc = (int)hipGetLastError())) return rc;
   const long nred = (long)g.cout * g.ks * g.ks * g.cin;
   // elements per block: >= ~512 blocks when possible; the rest of the block's threads split the splits
@@ -4437,6 +4522,15 @@ int64_t cgl_conv_packed_floats(int h, int w, int cin, int cout, int stride, int 
   const int np = dir ? bwd_probs(g, P) : fwd_probs(g, P);
   return pack_layout(P, np, nullptr);
 }
+
+int cgl_conv_set_mma_dtype(int dtype) {
+  if (dtype != CGL_DTYPE_F32 && dtype != CGL_DTYPE_BF16) return CGL_E_ARG;   // f16: no loss scaling in the conv round
+  if (cgl_launch_batch_open() || t_wdefer.on) return CGL_E_STATE;
+  t_mma_dtype = dtype;
+  return CGL_OK;
+}
+
+int cgl_conv_get_mma_dtype(void) { return t_mma_dtype; }
 
 int cgl_conv_wgrad_defer_begin(void) {
   if (t_wdefer.on) return CGL_E_STATE;
@@ -5243,3 +5337,4 @@ int cgl_counters_add(int* p, int n, int v, void* stream) {
 }
 
 }  // extern "C"
+#endif  // CGL_CONV_MMA_KERNELS_ONLY

@@ -335,7 +335,11 @@ int cgl_conv3x3_fwd(const float* X, const float* W, const float* bias, float* Y,
  * gradient dY[n][ho][wo][cout] of the convolution output (autograd of model/lsgan.py's convs). */
 int cgl_conv3x3_bwd_data(const float* dY, const float* W, float* dX, int n, int h, int w, int cin, int cout,
                          int stride, int up, void* workspace, int64_t ws_bytes, void* stream);
-/* dW[cout][cin][3][3] and db[cout] (may be null) of the convolution from dY and its input X. */
+/* dW[cout][cin][3][3] and db[cout] (may be null) of the convolution from dY and its input X.
+ * With bf16 MFMA operands (cgl_conv_set_mma_dtype) dY and the im2col values of X are rounded as they enter the
+ * MFMA.  The bias gradient then depends on where it is computed: where it rides the im2col ones-column of the
+ * MFMA kernel it is the column sum of the ROUNDED dY; where cgl_conv3x3_bias_by_colsum reports the column-sum
+ * path it stays the fp32 sum of the unrounded dY. */
 int cgl_conv3x3_bwd_weight(const float* dY, const float* X, float* dW, float* db, int n, int h, int w, int cin,
                            int cout, int stride, int up, void* workspace, int64_t ws_bytes, void* stream);
 /* cgl_conv3x3_bwd_weight with X the PRE-BatchNorm map of forward call in_group of in_groups: the convolution's
@@ -418,6 +422,21 @@ int cgl_conv_wgrad_defer_cancel(void);
  * completed-step count from *snap).  Nothing else in the launch may read the counters.  At most once per
  * deferral (CGL_E_STATE otherwise, or outside a deferral). */
 int cgl_conv_wgrad_defer_counters(int* counters, int n, int v, int* snap, int snap_index);
+
+/* Operand type of the MFMA convolution kernels for cgl_conv3x3_* calls issued from this thread
+ * from now on: CGL_DTYPE_F32 (default) or CGL_DTYPE_BF16.  CGL_DTYPE_F16 and anything else:
+ * CGL_E_ARG.  CGL_E_STATE while a launch batch (cgl_conv_batch_begin) or a weight-gradient
+ * deferral is open on this thread.  Read when a call is issued, so a captured graph keeps the
+ * type it was captured with.
+ * With CGL_DTYPE_BF16 every forward / input-gradient / weight-gradient variant (_packed, _stats, _bnin,
+ * _actdrop included) that reaches an MFMA kernel rounds each operand value to bf16 (round to nearest even) as it
+ * enters the MFMA -- after the padding masks, the folded BatchNorm + LeakyReLU of the _bnin forms and the phase
+ * combination of the packed weights, which stay fp32 in memory -- and accumulates in fp32; epilogues are
+ * unchanged.  bf16 has fp32's exponent range, so no loss scaling is involved (f16 would need it, hence the
+ * refusal).  Calls routed to the vector-ALU kernels (one input or one output channel) and all cgl_dense_* /
+ * cgl_linear_* calls ignore the mode. */
+int cgl_conv_set_mma_dtype(int dtype);
+int cgl_conv_get_mma_dtype(void);
 
 /* ---- device round log of the conv round ------------------------------------------------------
  * One completed conv round's scalars: what the reference prints after every communication round (F and Lambda,

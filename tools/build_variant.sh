@@ -13,5 +13,5 @@ for p in 1 2 3; do
 done
 wait
 /opt/rocm/bin/hipcc $FLAGS -shared build/var_$tag.o build/var_${tag}_p1.o build/var_${tag}_p2.o build/var_${tag}_p3.o \
-  build/cgl_conv_tu.o -o lib_$tag/libcglgan_hip.so
+  build/cgl_conv_tu.o build/cgl_conv_bf16.o -o lib_$tag/libcglgan_hip.so
 echo "built lib_$tag ($defs)"
