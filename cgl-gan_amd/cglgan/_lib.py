@@ -18,14 +18,16 @@ WEIGHT_CAPGAN, WEIGHT_MEAN, WEIGHT_MIX_SINGLE, WEIGHT_MIX_DOUBLE, WEIGHT_CGLGAN 
 PHASE_ALL, PHASE_A, PHASE_B = 0, 1, 2
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
 MODEL_G, MODEL_D = 0, 1
+MAX_COLOCATED = 16      # CGL_MAX_COLOCATED
 
 # every symbol include/cglgan.h declares (checked by tests/test_lib_exports.py)
 EXPORTS = [
     "cgl_gan_param_count", "cgl_gan_param_tensor", "cgl_gan_running_count", "cgl_gan_workspace_bytes",
-    "cgl_gan_create", "cgl_gan_destroy", "cgl_gan_reset", "cgl_gan_sync_params", "cgl_gan_sync_params_d", "cgl_gan_gemm_trace", "cgl_gan_run", "cgl_gan_run_graph", "cgl_gan_run_graph_rounds", "cgl_gan_prepare_graph_rounds",
+    "cgl_gan_create", "cgl_gan_create_sharded", "cgl_gan_destroy", "cgl_gan_reset", "cgl_gan_sync_params", "cgl_gan_sync_params_d", "cgl_gan_gemm_trace", "cgl_gan_run", "cgl_gan_run_graph", "cgl_gan_run_graph_rounds", "cgl_gan_prepare_graph_rounds",
     "cgl_gan_alpha_scale", "cgl_gan_exchange_mode", "cgl_gan_gather_buffers",
     "cgl_gan_exchange_buffer", "cgl_gan_tensor", "cgl_gan_read_stats",
     "cgl_gan_round_log_capacity", "cgl_gan_read_round_log",
+    "cgl_gan_read_stats_worker", "cgl_gan_read_round_log_worker",
     "cgl_gan_plan_info", "cgl_gan_launch_count", "cgl_gan_launch_info", "cgl_gan_launch_one", "cgl_gan_profile", "cgl_linear_fwd", "cgl_linear_bwd_data", "cgl_linear_bwd_weight", "cgl_adam_step",
     "cgl_normal_fill", "cgl_op_workspace_bytes", "cgl_version", "cgl_act_fwd", "cgl_act_bwd", "cgl_bn1d_fwd",
     "cgl_bn1d_bwd",
@@ -62,7 +64,8 @@ class GanConfig(ctypes.Structure):
                 ("beta2", ctypes.c_double), ("adam_eps", ctypes.c_double), ("bn_eps", ctypes.c_double),
                 ("bn_momentum", ctypes.c_double), ("slope", ctypes.c_float), ("seed", ctypes.c_ulonglong),
                 ("gen_z", ctypes.c_int), ("sample_n", ctypes.c_int), ("gemm_dtype", ctypes.c_int),
-                ("loss_scale", ctypes.c_float), ("scale_growth_interval", ctypes.c_int)]
+                ("loss_scale", ctypes.c_float), ("scale_growth_interval", ctypes.c_int),
+                ("colocated", ctypes.c_int)]
 
 
 class GanBuffers(ctypes.Structure):
@@ -149,6 +152,7 @@ def _load():
         "cgl_gan_running_count": (i64, [P(GanConfig)]),
         "cgl_gan_workspace_bytes": (i64, [P(GanConfig)]),
         "cgl_gan_create": (ci, [P(GanConfig), P(GanBuffers), P(vp)]),
+        "cgl_gan_create_sharded": (ci, [P(GanConfig), P(GanBuffers), P(i64), P(ci), P(vp)]),
         "cgl_gan_destroy": (ci, [vp]),
         "cgl_gan_reset": (ci, [vp, P(cf), vp]),
         "cgl_gan_sync_params": (ci, [vp, vp]),
@@ -164,6 +168,8 @@ def _load():
         "cgl_gan_exchange_buffer": (ci, [vp, P(vp), P(i64)]),
         "cgl_gan_tensor": (ci, [vp, ci, P(vp), P(i64)]),
         "cgl_gan_read_stats": (ci, [vp, P(GanStats), vp]),
+        "cgl_gan_read_stats_worker": (ci, [vp, ci, P(GanStats), vp]),
+        "cgl_gan_read_round_log_worker": (ci, [vp, ci, ci, ci, P(GanRoundRec), vp]),
         "cgl_gan_round_log_capacity": (ci, []),
         "cgl_gan_read_round_log": (ci, [vp, ci, ci, P(GanRoundRec), vp]),
         "cgl_gan_plan_info": (ci, [vp, ci, P(ci), P(ci), P(ctypes.c_double)]),

@@ -126,6 +126,25 @@ class DriverConfig:
     rounds_per_launch: int = 10      # rounds per hipGraph launch of a one-worker run (1 .. MAX_ROUNDS_PER_LAUNCH);
                                      #   the per-round log lines come from the device round log, so log_every does
                                      #   not shorten the launches.  Does not change the trajectory
+    colocate: bool = False           # ONE process runs all num_workers workers of the one server on its GPU (a
+                                     #   co-located GanStep: the reference's own layout, capgan.py:34-58); capgan /
+                                     #   mdgan, num_servers 1, world size 1
+
+    def __post_init__(self):
+        self._check_colocate()
+
+    def _check_colocate(self):
+        if not self.colocate:
+            return
+        if self.algo == "mixg":
+            raise ValueError("colocate: algo mixg is not supported (Mix-G's per-worker G heads are not planned in a "
+                             "co-located step); capgan or mdgan")
+        if self.num_servers != 1:
+            raise ValueError("colocate: num_servers must be 1 (one co-located step holds one server's workers)")
+        if self.loss_scale:
+            raise ValueError("colocate: loss_scale is not supported by the co-located step")
+        if self.algo in ALGOS and not 2 <= self.num_workers <= 16:
+            raise ValueError("colocate: num_workers must be in 2..16 (CGL_MAX_COLOCATED)")
 
     @classmethod
     def from_module(cls, **overrides):
@@ -138,6 +157,7 @@ class DriverConfig:
     def validate(self):
         if self.algo not in ALGOS:
             raise ValueError(f"algo must be one of {ALGOS}")
+        self._check_colocate()
         if self.num_servers < 1 or self.num_workers % self.num_servers:
             raise ValueError("num_workers must be a positive multiple of num_servers (capgan.py:509-516 drops "
                              "the remainder workers; here every GPU is a worker)")
@@ -226,6 +246,32 @@ def gpu_step(cfg: DriverConfig, topo: Topology, shard: torch.Tensor, beta, g_sd,
     return step
 
 
+def colocated_step(cfg: DriverConfig, x: torch.Tensor, shards, beta, g_sd, d_sds, device):
+    """The co-located fused round (GanStep(colocated=num_workers)) of a one-process run: the workers' shards back to
+    back in one resident buffer, each sampled on device as its own worker's ``gpu_step`` would, every worker's D
+    loaded with its own initial state."""
+    from . import specs
+    from .step import GanStep
+    img = cfg.img_size ** 2
+    gm = specs.mnist_generator(img)
+    dm = specs.mnist_discriminator(img, sigmoid=(cfg.algo == "mdgan"))
+    lens = [len(s) for s in shards]
+    if min(lens) == 0:
+        raise ValueError(f"worker {lens.index(0)}: empty shard")
+    real = torch.cat([x[torch.as_tensor(s)] for s in shards]).to(device=device, dtype=torch.float32).contiguous()
+    table, row0 = [], 0
+    for n in lens:
+        table.append((row0, n))
+        row0 += n
+    step = GanStep(gm, dm, batch=cfg.batch_size, epoch=cfg.epoch, loss="bce" if cfg.algo == "mdgan" else "ce",
+                   weighting=cfg.weighting_, colocated=cfg.num_workers, lr_g=cfg.lr_g, lr_d=cfg.lr_d,
+                   betas=(cfg.b1, cfg.b2), seed=cfg.seed, gen_z=True, real=real, sample_n=max(lens), shards=table,
+                   device=device, gemm_dtype=cfg.gemm_dtype)
+    step.load_state_dicts(g_sd, list(d_sds))
+    step.reset(beta=beta)
+    return step
+
+
 def capgan_cloud_schedule(cfg: DriverConfig, srv_lens, server: int):
     """The Cloud schedule of a multi-server CAPGAN run (capgan.py:169, Cloud.run :99-117).
 
@@ -260,6 +306,9 @@ class Driver:
         dist_on = dist.is_available() and dist.is_initialized()
         self.rank = rank if rank is not None else (dist.get_rank() if dist_on else 0)
         self.world = world if world is not None else (dist.get_world_size() if dist_on else 1)
+        if cfg.colocate:
+            self._init_colocated(device)
+            return
         if self.world != cfg.num_workers:
             raise ValueError(f"one process per worker: world size {self.world} != num_workers {cfg.num_workers}")
         self.topo = topo = Topology(cfg.num_workers, cfg.num_servers, self.rank)
@@ -300,6 +349,32 @@ class Driver:
                 except Exception as e:        # raised on every rank together below, not here alone
                     err = e
             self._check_resumed_round(err)
+
+    def _init_colocated(self, device):
+        """``colocate``: this one process is the server and all its workers (one co-located step), with the shards,
+        beta weights and initial models of the num_workers-process run."""
+        from .data import beta_weights
+        from .exchange import ColocatedExchange
+        from .init import topology_state
+        cfg = self.cfg
+        if self.world != 1:
+            raise ValueError(f"colocate: one process runs every worker, world size must be 1 (it is {self.world})")
+        self.rank = 0
+        self.topo = Topology(cfg.num_workers, 1, 0)
+        x, shards = make_shards(cfg)
+        self.beta, _ = beta_weights([len(s) for s in shards])
+        self.beta = self.beta.tolist()
+        gs, ds = topology_state(cfg.algo, 1, cfg.num_workers, cfg.seed, cfg.img_size ** 2)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.step = colocated_step(cfg, x, shards, self.beta, gs[0], ds, device)
+        self.exchange = ColocatedExchange(self.step, share_every=cfg.share_every, swap_every=cfg.swap_every,
+                                          server_rank=0)
+        self.lambda_list = []
+        self.round = 0
+        if cfg.resume_dir:
+            if os.path.exists(self.resume_path()):
+                self.load_resume()
 
     def run(self, rounds: int = None, log=print):
         """``rounds`` communication rounds (default: num_communication), as Server.run's
@@ -388,7 +463,10 @@ class Driver:
 
     def _resume_key(self):
         c = self.cfg
-        return json.dumps({k: getattr(c, k) for k in self.RESUME_KEYS}, sort_keys=True)
+        key = {k: getattr(c, k) for k in self.RESUME_KEYS}
+        if c.colocate:                  # (a co-located run's file holds every worker: its own kind of file)
+            key["colocate"] = True
+        return json.dumps(key, sort_keys=True)
 
     def _rng_states(self):
         """The exchange's host-side generators (the MD-GAN D-swap's Random(server + 100)) as plain lists
@@ -470,6 +548,8 @@ def parse_args(argv=None):
                    help=f"rounds per hipGraph launch of a one-worker run (1..{MAX_ROUNDS_PER_LAUNCH}); the per-round "
                         "log lines are read from the device round log after each launch")
     p.add_argument("--eager", action="store_true", help="launch the round without hipGraph replay")
+    p.add_argument("--colocate", action="store_true",
+                   help="one process runs all num_workers workers of the one server on its GPU (capgan / mdgan)")
     p.add_argument("--gemm_dtype", default="f32", choices=["f32", "f16", "bf16"],
                    help="GEMM operand type (f16 / bf16: 16-bit operands, fp32 accumulation; BASELINE config 5)")
     p.add_argument("--loss_scale", type=float, default=0.0,

@@ -431,6 +431,74 @@ class LocalComm:
         return None
 
 
+class ColocatedExchange:
+    """The round loop of a co-located step (``GanStep(colocated=W)``: the W workers of one server in one context, the
+    gradient exchange inside the round itself) with ``WorkerExchange``'s ``round`` / ``rounds`` interface.  What is
+    left to exchange is D: the E-share (mean of the W parameter blocks, summed in worker order and divided by W, as
+    ``LocalComm`` does) every ``share_every`` rounds and the MD-GAN D-swap (``DSwap`` permutation of the blocks;
+    parameters only, each worker keeps its Adam state) every ``swap_every`` rounds -- stream-ordered torch ops on
+    ``step.d_params`` followed by ``sync_params_d()``.  ``rounds`` issues multi-round graph launches cut after every
+    round that ends with a share or a swap."""
+
+    comm = None
+    cloud = None
+
+    def __init__(self, step, share_every: int = 0, swap_every: int = 0, server_rank: int = 0):
+        W = int(getattr(step, "colocated", 0) or 0)
+        if W < 2:
+            raise ValueError("ColocatedExchange drives a co-located step (GanStep(colocated=W), W >= 2)")
+        self.step, self.size = step, W
+        self.share_every, self.swap_every = int(share_every), int(swap_every)
+        self.dswap = DSwap(W, server_rank) if self.swap_every > 0 else None
+
+    def _due(self, r):
+        """(share, swap) after round r (0-based), as WorkerExchange.round decides them."""
+        return (self.share_every > 0 and (r + 1) % self.share_every == 0,
+                self.swap_every > 0 and (r + 1) % self.swap_every == 0)
+
+    def chunks(self, r0: int, n: int):
+        """Rounds r0 .. r0 + n - 1 as launch lengths: a launch ends with the first of its rounds after which D is
+        shared or swapped (the exchange runs between launches).  The lengths sum to n."""
+        out, run = [], 0
+        for r in range(r0, r0 + max(0, int(n))):
+            run += 1
+            if any(self._due(r)):
+                out.append(run)
+                run = 0
+        if run:
+            out.append(run)
+        return out
+
+    @torch.no_grad()
+    def _d_exchange(self, r):
+        share, swap = self._due(r)
+        dp = self.step.d_params                 # [W, nd]
+        if share:
+            tot = dp[0].clone()
+            for w in range(1, self.size):
+                tot += dp[w]
+            tot /= self.size
+            dp.copy_(tot.unsqueeze(0).expand_as(dp))
+        perm = None
+        if swap:                                # worker i continues with D_{perm[i]}
+            perm = self.dswap.next_perm()
+            dp.copy_(dp[torch.as_tensor(perm, device=dp.device)])
+        if share or swap:
+            self.step.sync_params_d()
+        return perm
+
+    def round(self, r: int, graph: bool = True):
+        self.step.run(C.PHASE_ALL, graph=graph)
+        return self._d_exchange(r)
+
+    def rounds(self, r0: int, n: int, graph: bool = True):
+        r = r0
+        for m in self.chunks(r0, n):
+            self.step.run_rounds(m, graph=graph)
+            r += m
+            self._d_exchange(r - 1)
+
+
 def local_cloud_average(steps, weights, cloud_scope: str = "trunk", segema: float = 0.0,
                         fedavg_compat_noop: bool = False):
     """``WorkerExchange.cloud_average`` over in-process workers (the cloud group = ``steps``, one

@@ -55,6 +55,19 @@ class GanStep:
     caller on the raw buffer -- must be followed by ``sync_params()`` (both models) or ``sync_params_d()`` (D only);
     otherwise the next rounds run on the old weights.  (G's copies are re-packed inside every round by the forward
     BatchNorm / loss-head launches; D's copies and the next round's z are the ones a missed write leaves stale.)
+
+    Co-located workers (``colocated=W``, 2 .. ``_lib.MAX_COLOCATED``): this one step runs the W-worker round of a
+    server group on one device (the reference's own default: ten Workers, one Server on ``cuda:0``,
+    capgan.py:34-58) -- one generator, computed once, and the W workers' discriminators, every D stage one launch
+    over the W workers, the exchange local (cgl_gan_config.colocated in include/cglgan.h).  Then ``n_workers`` is W,
+    ``d_params`` / ``d_grads`` / ``d_m`` / ``d_v`` are ``[W, nd]``, ``d_views`` / ``d_grad_views`` are lists of W
+    key-view dicts, ``load_state_dicts`` takes a list of W discriminator state dicts, ``d_state_dict(w)``,
+    ``stats(worker=w)``, ``read_log`` / ``losses_log(..., worker=w)`` report worker w (default 0).  Without the
+    sampler ``real`` is ``[W, epoch * batch_real, img]``; with it (``sample_n`` > 0) either W shards of ``sample_n``
+    rows back to back, or ``shards=[(row0, rows), ...]`` into ``real`` -- worker w then draws the index stream a
+    one-worker step over its shard draws with the same seed.  ``run``, ``run_rounds``, ``prepare_rounds``,
+    ``resume_state`` / ``load_resume_state`` and ``sync_params`` work as on the one-worker step; the ``.data``-write
+    caveat above and the version-counter refresh cover the whole ``[W, nd]`` block.
     """
 
     def __init__(self, g: MlpModel, d: MlpModel, batch: int, batch_real: int = None, epoch: int = 1,
@@ -63,7 +76,7 @@ class GanStep:
                  adam_eps: float = 1e-8, bn_eps: float = 0.8, bn_momentum: float = 0.1, slope: float = 0.2,
                  seed: int = 20211212, gen_z: bool = False, real: torch.Tensor = None, sample_n: int = 0,
                  real_idx: torch.Tensor = None, device="cuda", gemm_dtype: str = "f32", loss_scale: float = 0.0,
-                 scale_growth_interval: int = 2000):
+                 scale_growth_interval: int = 2000, colocated: int = 0, shards=None):
         """``gemm_dtype``: "f32" (the reference arithmetic), or "f16" / "bf16": every GEMM operand
         rounded to 16 bits at the matrix core with fp32 accumulation (BASELINE config 5's fp16;
         fp32 master weights, BatchNorm, losses and Adam; outside the fp32 parity band).
@@ -73,6 +86,20 @@ class GanStep:
         before Adam, a round whose gradients hold an inf / NaN skips that model's Adam step and halves
         its scale, ``scale_growth_interval`` clean rounds double it (include/cglgan.h)."""
         self.gm, self.dm = g, d
+        W = int(colocated) if colocated and int(colocated) > 1 else 0
+        self.colocated = W
+        if W:
+            if W > C.MAX_COLOCATED:
+                raise ValueError(f"colocated: at most {C.MAX_COLOCATED} workers share a step")
+            if exchange_layer != -1:
+                raise ValueError("colocated: the G-output exchange only (Mix-G's per-worker heads are not planned)")
+            if loss_scale:
+                raise ValueError("colocated: loss scaling is not supported")
+            if n_workers not in (1, W) or rank != 0:
+                raise ValueError("colocated: the step is the whole group (n_workers = colocated, rank 0)")
+            n_workers = W
+        elif shards is not None:
+            raise ValueError("shards: a co-located step's sampler table")
         self.B = batch
         self.Br = batch_real or batch
         self.epoch = epoch
@@ -94,6 +121,7 @@ class GanStep:
         if loss_scale and gemm_dtype == "f32":
             raise ValueError("loss_scale applies to the 16-bit GEMM paths (gemm_dtype f16 / bf16)")
         cfg.loss_scale, cfg.scale_growth_interval = float(loss_scale), int(scale_growth_interval)
+        cfg.colocated = W
         self.cfg = cfg
         self.n_workers, self.rank = n_workers, rank
         self.exchange_layer = exchange_layer
@@ -109,12 +137,27 @@ class GanStep:
         self.g_params, self.g_grads = torch.zeros(ng, **f32), torch.zeros(ng, **f32)
         self.g_m, self.g_v = torch.zeros(ng, **f32), torch.zeros(ng, **f32)
         self.g_running = torch.zeros(max(nr, 1), **f32)
-        self.d_params, self.d_grads = torch.zeros(nd, **f32), torch.zeros(nd, **f32)
-        self.d_m, self.d_v = torch.zeros(nd, **f32), torch.zeros(nd, **f32)
+        dshape = (W, nd) if W else (nd,)
+        self.d_params, self.d_grads = torch.zeros(dshape, **f32), torch.zeros(dshape, **f32)
+        self.d_m, self.d_v = torch.zeros(dshape, **f32), torch.zeros(dshape, **f32)
         self.z = torch.zeros(2 * batch, g.dims[0], **f32)
         img = g.dims[-1]
         if real is None:
-            real = torch.zeros(epoch * self.Br, img, **f32)
+            real = torch.zeros((W, epoch * self.Br, img) if W else (epoch * self.Br, img), **f32)
+        if W:
+            nrows = real.numel() // img
+            if not real.is_contiguous():
+                raise ValueError("colocated: real must be contiguous")
+            if sample_n > 0:
+                shards = [(w * sample_n, sample_n) for w in range(W)] if shards is None else [
+                    (int(a), int(b)) for a, b in shards]
+                if len(shards) != W or any(a < 0 or b < 1 or a + b > nrows for a, b in shards):
+                    raise ValueError("colocated: one (row0, rows) shard inside real per worker")
+            elif shards is not None:
+                raise ValueError("shards: needs the device sampler (sample_n > 0)")
+            elif nrows < W * epoch * self.Br and real_idx is None:
+                raise ValueError("colocated: real holds [W, epoch * batch_real] rows")
+        self.shards = shards
         self.real = real
         self.real_idx = real_idx
         self.losses_all = torch.zeros(max(n_workers, 1), **f32)
@@ -128,13 +171,23 @@ class GanStep:
         bufs.workspace_bytes = wsb
         self._bufs = bufs
         h = ctypes.c_void_p()
-        C.check(C.lib.cgl_gan_create(ctypes.byref(cfg), ctypes.byref(bufs), ctypes.byref(h)), "cgl_gan_create")
+        if W and sample_n > 0:
+            row0 = (ctypes.c_int64 * W)(*[a for a, _ in shards])
+            rows = (ctypes.c_int * W)(*[b for _, b in shards])
+            C.check(C.lib.cgl_gan_create_sharded(ctypes.byref(cfg), ctypes.byref(bufs), row0, rows, ctypes.byref(h)),
+                    "cgl_gan_create_sharded")
+        else:
+            C.check(C.lib.cgl_gan_create(ctypes.byref(cfg), ctypes.byref(bufs), ctypes.byref(h)), "cgl_gan_create")
         self._h = h
         self._pk_ver = None        # the packed weight copies (G, D): refreshed before the first round (sync_params)
         self.g_views = self._views(g, C.MODEL_G, self.g_params)
-        self.d_views = self._views(d, C.MODEL_D, self.d_params)
         self.g_grad_views = self._views(g, C.MODEL_G, self.g_grads)
-        self.d_grad_views = self._views(d, C.MODEL_D, self.d_grads)
+        if W:
+            self.d_views = [self._views(d, C.MODEL_D, self.d_params[w]) for w in range(W)]
+            self.d_grad_views = [self._views(d, C.MODEL_D, self.d_grads[w]) for w in range(W)]
+        else:
+            self.d_views = self._views(d, C.MODEL_D, self.d_params)
+            self.d_grad_views = self._views(d, C.MODEL_D, self.d_grads)
         self._running_views()
         self.reset()
 
@@ -197,10 +250,18 @@ class GanStep:
 
     @torch.no_grad()
     def load_state_dicts(self, g_sd, d_sd):
+        """``d_sd``: D's state dict; co-located: a list of W of them (worker order)."""
         for k, v in self.g_views.items():
             v.copy_(g_sd[k].reshape(v.shape))
-        for k, v in self.d_views.items():
-            v.copy_(d_sd[k].reshape(v.shape))
+        if self.colocated:
+            if len(d_sd) != self.colocated:
+                raise ValueError(f"co-located step: one D state dict per worker ({self.colocated})")
+            pairs = list(zip(self.d_views, d_sd))
+        else:
+            pairs = [(self.d_views, d_sd)]
+        for views, sd in pairs:
+            for k, v in views.items():
+                v.copy_(sd[k].reshape(v.shape))
         for k, v in self.running.items():
             if k in g_sd:
                 v.copy_(g_sd[k])
@@ -231,8 +292,9 @@ class GanStep:
         d.load_state_dict(self.d_state_dict())
         return g, d
 
-    def d_state_dict(self):
-        return OrderedDict((k, v.detach().clone()) for k, v in self.d_views.items())
+    def d_state_dict(self, worker: int = 0):
+        views = self.d_views[worker] if self.colocated else self.d_views
+        return OrderedDict((k, v.detach().clone()) for k, v in views.items())
 
     # ------------------------------------------------------------------ resume
     _RESUME_BUFS = ("g_params", "g_m", "g_v", "g_running", "d_params", "d_m", "d_v")
@@ -364,9 +426,10 @@ class GanStep:
             raise RuntimeError("address outside the context workspace")
         return self.workspace[off:off + 4 * n].view(torch.float32)
 
-    def stats(self):
+    def stats(self, worker: int = 0):
         s = C.GanStats()
-        C.check(C.lib.cgl_gan_read_stats(self._h, ctypes.byref(s), _stream()), "cgl_gan_read_stats")
+        C.check(C.lib.cgl_gan_read_stats_worker(self._h, int(worker), ctypes.byref(s), _stream()),
+                "cgl_gan_read_stats")
         return {"round": s.round, "d_loss": list(s.d_loss)[:self.epoch], "d_real": list(s.d_real)[:self.epoch],
                 "d_fake": list(s.d_fake)[:self.epoch], "g_loss": s.g_loss, "alpha": s.alpha, "F": s.F,
                 "lambda": s.lambda_, "bn_batches": s.bn_batches, "loss_scale": list(s.loss_scale),
@@ -377,7 +440,7 @@ class GanStep:
         """Rounds the device round log keeps (a ring: round r overwrites round r - log_capacity)."""
         return C.lib.cgl_gan_round_log_capacity()
 
-    def losses_log(self, first: int, count: int):
+    def losses_log(self, first: int, count: int, worker: int = 0):
         """The scalars of rounds ``first`` .. ``first + count - 1`` (1-based, as ``stats()["round"]`` after each), one
         dict per round, read from the device round log with one copy (two when the range wraps in the ring) and
         one stream synchronise -- what the reference prints after every communication round (capgan.py:177-183),
@@ -385,10 +448,11 @@ class GanStep:
         ``d_real``, ``d_fake``, ``g_loss``, ``alpha``, ``F``, ``lambda``, ``loss_scale``) plus ``real_rows`` (the
         sampler's rows per local D step) and ``step_skipped`` (``stats()["last_skipped"]`` right after that
         round).  LookupError when a round of the range is not in the log (not run yet, overwritten, or cleared
-        by ``reset`` / ``load_resume_state``); ValueError for a range no read can take."""
-        return self.log_dicts(self.read_log(first, count))
+        by ``reset`` / ``load_resume_state``); ValueError for a range no read can take.  ``worker``: whose records,
+        on a co-located step (each worker has its own ring)."""
+        return self.log_dicts(self.read_log(first, count, worker))
 
-    def read_log(self, first: int, count: int):
+    def read_log(self, first: int, count: int, worker: int = 0):
         """The raw records (``_lib.GanRoundRec`` array, a host copy of its own) of ``losses_log``'s range: the
         device read without the conversion, for a caller that formats them later (``log_dicts``)."""
         first, count = int(first), int(count)
@@ -399,7 +463,7 @@ class GanStep:
         if getattr(self, "_log_host", None) is None:     # page-locked: the copy goes straight to it, no staging
             self._log_host = torch.empty(cap * ctypes.sizeof(C.GanRoundRec), dtype=torch.uint8, pin_memory=True)
         buf = (C.GanRoundRec * count).from_address(self._log_host.data_ptr())
-        rc = C.lib.cgl_gan_read_round_log(self._h, first, count, buf, _stream())
+        rc = C.lib.cgl_gan_read_round_log_worker(self._h, int(worker), first, count, buf, _stream())
         if rc == -2:
             raise LookupError(f"rounds {first}..{first + count - 1} are not all in the round log (capacity {cap} "
                               "rounds: not run yet, overwritten, or cleared by reset / a resume load)")

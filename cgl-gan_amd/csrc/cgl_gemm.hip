@@ -821,6 +821,44 @@ __global__ __launch_bounds__(CGL_GEMM_THREADS) void cgl_gemm_f32(const CglGemmDe
   asm volatile("" ::"v"(pfv));
 }
 
+// The same problems for W co-located workers in one launch: descs = [W][q] (q <= 3 problems per worker, the W
+// copies of a problem identical in shape, layout and tiles, different in their pointers), every worker owning wpw
+// consecutive workgroups.  A workgroup finds its worker by one division and its problem among the worker's q by
+// the scalar selection (first workgroup of problems 1 and 2 within a worker, layout | vec << 2 per problem), then
+// runs the body of cgl_gemm_f32 on that descriptor -- whose wg_begin counts from the start of the launch -- so
+// each worker's result is bitwise what its own launch of the q problems computes.
+template <int TM, int TN, int DT = CGL_DTYPE_F32>
+__global__ __launch_bounds__(CGL_GEMM_THREADS) void cgl_gemm_grp(const CglGemmDesc* __restrict__ descs, int wpw, int q,
+                                                                 int sel_wg1, int sel_wg2, int sel_meta,
+                                                                 const int* __restrict__ pf, int pf_lines) {
+  extern __shared__ float cgl_dyn_lds[];
+  __shared__ double s_bnd[4 * TN * 32 * 2];
+  const int bid = blockIdx.x;
+  int pfv = 0;     // the next GEMM launch's descriptors into every XCD's L2 (as cgl_gemm_f32)
+  if (bid < 8 && (int)threadIdx.x < pf_lines) pfv = pf[threadIdx.x * 32];
+  const int w = bid / wpw, lb = bid - w * wpw;
+  const int di = lb >= sel_wg2 ? 2 : (lb >= sel_wg1 ? 1 : 0);
+  const CglGemmDesc* __restrict__ d = descs + w * q + di;
+  const int meta = (sel_meta >> (4 * di)) & 15;
+  const int layout = meta & 3;
+  const int vec = (meta >> 2) & 1;
+#define CGL_BODY_GRP(L)                                        \
+  do {                                                         \
+    if (vec)                                                   \
+      cgl_gemm_body<L, 1, TM, TN, DT>(d, bid, cgl_dyn_lds, s_bnd);  \
+    else                                                       \
+      cgl_gemm_body<L, 0, TM, TN, DT>(d, bid, cgl_dyn_lds, s_bnd);  \
+  } while (0)
+  if (layout == 0)
+    CGL_BODY_GRP(0);
+  else if (layout == 1)
+    CGL_BODY_GRP(1);
+  else
+    CGL_BODY_GRP(2);
+#undef CGL_BODY_GRP
+  asm volatile("" ::"v"(pfv));
+}
+
 // One problem whose descriptor travels in the kernel arguments (the single-op entry points cgl_linear_*):
 // nothing is uploaded before the launch, so the ops need no host synchronisation and can be captured into
 // a graph.  fp32, no deferred head.

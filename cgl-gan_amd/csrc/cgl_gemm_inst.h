@@ -14,6 +14,9 @@
 #define CGL_INST_F32(TM, TN, DT) \
   CGL_INST_PREFIX __global__ void cgl_gemm_f32<TM, TN, DT>(const CglGemmDesc* __restrict__, int, int, int, int, \
                                                            const int* __restrict__, int);
+#define CGL_INST_GRP(TM, TN, DT) \
+  CGL_INST_PREFIX __global__ void cgl_gemm_grp<TM, TN, DT>(const CglGemmDesc* __restrict__, int, int, int, int, int, \
+                                                           const int* __restrict__, int);
 #define CGL_INST_ARG(TM, TN) \
   CGL_INST_PREFIX __global__ void cgl_gemm_f32_arg<TM, TN>(const CglGemmDesc);
 #define CGL_INST_PRO(TM, TN)                                                                                    \
@@ -42,7 +45,18 @@ CGL_INST_F32(2, 2, CGL_DTYPE_BF16)
 CGL_INST_ADAM(1, 1)
 CGL_INST_ADAM(2, 2)
 #endif
+#if CGL_IN_PART(4)   // the co-located workers' grouped launches, fp32
+CGL_INST_GRP(1, 1, CGL_DTYPE_F32)
+CGL_INST_GRP(2, 2, CGL_DTYPE_F32)
+#endif
+#if CGL_IN_PART(5)   // the same, 16-bit operands
+CGL_INST_GRP(1, 1, CGL_DTYPE_F16)
+CGL_INST_GRP(2, 2, CGL_DTYPE_F16)
+CGL_INST_GRP(1, 1, CGL_DTYPE_BF16)
+CGL_INST_GRP(2, 2, CGL_DTYPE_BF16)
+#endif
 
+#undef CGL_INST_GRP
 #undef CGL_INST_F32
 #undef CGL_INST_ARG
 #undef CGL_INST_PRO

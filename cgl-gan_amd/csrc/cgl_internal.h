@@ -236,6 +236,16 @@ struct CglBnBwdDesc {
 #define CGL_MAX_EPOCH 8
 #define CGL_MAX_WORKERS 64
 
+// Co-located workers (cgl_gan_config.colocated = W): the per-worker buffers of workers 1 .. W - 1 repeat worker 0's
+// in the same order, so one offset per worker (in elements, from worker 0's buffer) addresses any of them in the
+// grouped launches (D's packed weight copies, the sampler's index lists); sampler shards by their row counts.
+struct CglCoOff { long d[CGL_MAX_COLOCATED]; };
+struct CglCoShard {
+  int nw;
+  int rows[CGL_MAX_COLOCATED];      // rows of worker w's shard
+  long idx_off[CGL_MAX_COLOCATED];  // worker w's index list [epoch][batch_real], in ints from worker 0's
+};
+
 // Per-context device scalar block.  Written only by cgl_step_begin (counters, Adam bias
 // corrections), by the head kernels' last workgroup (losses), by cgl_alpha_scale and by
 // the scalar tail of the G Adam launch; every other kernel only reads it.

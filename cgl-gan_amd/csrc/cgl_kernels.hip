@@ -488,6 +488,14 @@ __device__ __forceinline__ void cgl_bn_bwd_body(const CglBnBwdDesc* __restrict__
 __global__ __launch_bounds__(256) void cgl_head_loss(const CglHeadDesc d) {
   cgl_head_loss_body(&d, blockIdx.x, gridDim.x);
 }
+// The loss heads of the W co-located workers as one launch: workgroups [w wgs, (w + 1) wgs) run worker w's head
+// (descriptor heads[w] in memory: same shape for every worker, its own activations, D output layer, partials and
+// ticket counter), each the one-head kernel's body -- so worker w's losses and gradients are bitwise those of its
+// own cgl_head_loss launch.  The last-arriver reduction stays per worker (no workgroup waits for another).
+__global__ __launch_bounds__(256) void cgl_head_loss_grp(const CglHeadDesc* __restrict__ heads, int wgs) {
+  const int w = blockIdx.x / wgs;
+  cgl_head_loss_body(heads + w, (int)blockIdx.x - w * wgs, wgs);
+}
 __global__ __launch_bounds__(256) void cgl_bn_apply(const CglBnApplyDesc d) {
   cgl_bn_apply_body(&d, blockIdx.x, blockIdx.y);
 }
@@ -643,6 +651,10 @@ struct CglAdamArgs {
   // the round log (set on the round's tail launch only, null elsewhere): the thread that runs cgl_round_tail
   // then writes the completed round's record into slot (round - 1) % CGL_ROUND_LOG_CAP
   cgl_gan_round_rec* log;
+  // co-located workers (nw >= 2, else 0): the state blocks st[0 .. nw) and the rings log + w CGL_ROUND_LOG_CAP are
+  // contiguous; the tail writes every worker's record (losses and real_rows from st[w], alpha from st[0].alphas[w],
+  // F / lambda / round from the shared server state st[0])
+  int nw;
 };
 __device__ __forceinline__ bool cgl_adam_zblock(const CglAdamArgs& a, const CglStepState* st) {
   if (!a.znext || (int)blockIdx.x < a.zblk0) return false;
@@ -686,7 +698,11 @@ __device__ float cgl_tail_alpha(const CglStepState* st, int mode, float lam, int
   for (int q = 0; q < N; ++q) s += expf(cgl_tail_arg(st, mode, lam, q) - mx);
   return expf(cgl_tail_arg(st, mode, lam, i) - mx) / s;
 }
-__device__ void cgl_round_tail(CglStepState* st) {
+// alphas_ready (a co-located context's tail): st->alphas already holds this round's alpha_q -- cgl_alpha_combine,
+// an earlier launch of the same round, computed them from the same losses, lambda and beta with cgl_weights, whose
+// arithmetic cgl_tail_alpha repeats -- so F takes them from there instead of recomputing each one (O(N^3) expf
+// calls in this one thread: 0.38 ms of a 0.74 ms round at N = 10, profiles/colocated_ab.txt).
+__device__ void cgl_round_tail(CglStepState* st, bool alphas_ready = false) {
   const int N = st->n_workers;
   const float lam = st->lambda;
   const int mode = st->weighting;
@@ -710,7 +726,8 @@ __device__ void cgl_round_tail(CglStepState* st) {
     st->lambda = lam + 10.f * (g1 - g2);
   } else {
     float s = 0.f;
-    for (int q = 0; q < N; ++q) s += cgl_tail_alpha(st, mode, lam, q) * cgl_tail_loss(st, q);
+    for (int q = 0; q < N; ++q)
+      s += (alphas_ready ? st->alphas[q] : cgl_tail_alpha(st, mode, lam, q)) * cgl_tail_loss(st, q);
     st->F = s - 0.001f * lam;
     // optim.SGD([Lambda], lr=0.1): dF/dLambda = -0.001
     st->lambda = lam + (-0.1f) * (-0.001f);
@@ -732,37 +749,45 @@ __device__ void cgl_round_tail(CglStepState* st) {
 #define CGL_ST_W(f) ((int)(offsetof(CglStepState, f) / 4))
 #define CGL_REC_W(f) ((int)(offsetof(cgl_gan_round_rec, f) / 4))
 __device__ __forceinline__ void cgl_round_end(const CglAdamArgs& a, CglStepState* st, long t) {
+  const int nw = a.nw > 1 ? a.nw : 1;
   if (t == 0) {
-    cgl_round_tail(st);
+    cgl_round_tail(st, a.nw > 1);
     if (a.scale) st->scaler_pending = 1;   // GradScaler.update runs in the next round's prologue
     if (a.log) {
       const int r = st->round;
-      CGL_GLOBAL cgl_gan_round_rec* rec = (CGL_GLOBAL cgl_gan_round_rec*)a.log + ((unsigned)(r - 1) % CGL_ROUND_LOG_CAP);
-      rec->F = st->F;
-      rec->lambda_ = st->lambda;
-      rec->round = r;
+      for (int w = 0; w < nw; ++w) {
+        CGL_GLOBAL cgl_gan_round_rec* rec = (CGL_GLOBAL cgl_gan_round_rec*)a.log + (long)w * CGL_ROUND_LOG_CAP +
+                                            ((unsigned)(r - 1) % CGL_ROUND_LOG_CAP);
+        rec->F = st->F;
+        rec->lambda_ = st->lambda;
+        rec->round = r;
+      }
     }
   } else if (a.log && t >= 64 && t < 64 + 38) {
     const int w = (int)t - 64;
-    const CGL_GLOBAL unsigned int* s = (const CGL_GLOBAL unsigned int*)st;
-    const unsigned int r = s[CGL_ST_W(cur_round)];
-    CGL_GLOBAL unsigned int* d =
-        (CGL_GLOBAL unsigned int*)((CGL_GLOBAL cgl_gan_round_rec*)a.log + ((r - 1u) % CGL_ROUND_LOG_CAP));
-    if (w < 36) {
-      int so, dw;
-      if (w < 8) so = CGL_ST_W(d_loss) + w, dw = CGL_REC_W(d_loss) + w;
-      else if (w < 16) so = CGL_ST_W(d_loss_parts) + 2 * (w - 8), dw = CGL_REC_W(d_real) + (w - 8);
-      else if (w < 24) so = CGL_ST_W(d_loss_parts) + 2 * (w - 16) + 1, dw = CGL_REC_W(d_fake) + (w - 16);
-      else if (w == 24) so = CGL_ST_W(g_loss_parts), dw = CGL_REC_W(g_loss);
-      else if (w == 25) so = CGL_ST_W(alpha), dw = CGL_REC_W(alpha);
-      else if (w < 34) so = CGL_ST_W(real_rows) + (w - 26), dw = CGL_REC_W(real_rows) + (w - 26);
-      else so = CGL_ST_W(scale) + (w - 34), dw = CGL_REC_W(loss_scale) + (w - 34);
-      d[dw] = s[so];
-    } else {
-      // a.scale set: this round's own found flag (its update is pending); else scaling is off (always 0)
-      const int m = w - 36;
-      d[CGL_REC_W(step_skipped) + m] =
-          a.scale ? (s[CGL_ST_W(found) + m] != 0u ? 1u : 0u) : s[CGL_ST_W(last_skipped) + m];
+    const CGL_GLOBAL unsigned int* s0 = (const CGL_GLOBAL unsigned int*)st;
+    const unsigned int r = s0[CGL_ST_W(cur_round)];
+    for (int q = 0; q < nw; ++q) {
+      const CGL_GLOBAL unsigned int* s = (const CGL_GLOBAL unsigned int*)(st + q);
+      CGL_GLOBAL unsigned int* d = (CGL_GLOBAL unsigned int*)((CGL_GLOBAL cgl_gan_round_rec*)a.log +
+                                                              (long)q * CGL_ROUND_LOG_CAP + ((r - 1u) % CGL_ROUND_LOG_CAP));
+      if (w < 36) {
+        int so, dw;
+        if (w < 8) so = CGL_ST_W(d_loss) + w, dw = CGL_REC_W(d_loss) + w;
+        else if (w < 16) so = CGL_ST_W(d_loss_parts) + 2 * (w - 8), dw = CGL_REC_W(d_real) + (w - 8);
+        else if (w < 24) so = CGL_ST_W(d_loss_parts) + 2 * (w - 16) + 1, dw = CGL_REC_W(d_fake) + (w - 16);
+        else if (w == 24) so = CGL_ST_W(g_loss_parts), dw = CGL_REC_W(g_loss);
+        else if (w == 25) so = CGL_ST_W(alpha), dw = CGL_REC_W(alpha);
+        else if (w < 34) so = CGL_ST_W(real_rows) + (w - 26), dw = CGL_REC_W(real_rows) + (w - 26);
+        else so = CGL_ST_W(scale) + (w - 34), dw = CGL_REC_W(loss_scale) + (w - 34);
+        // (co-located: every worker's alpha is in the server state's alphas[], written by cgl_alpha_combine)
+        d[dw] = (a.nw > 1 && w == 25) ? s0[CGL_ST_W(alphas) + q] : s[so];
+      } else {
+        // a.scale set: this round's own found flag (its update is pending); else scaling is off (always 0)
+        const int m = w - 36;
+        d[CGL_REC_W(step_skipped) + m] =
+            a.scale ? (s[CGL_ST_W(found) + m] != 0u ? 1u : 0u) : s[CGL_ST_W(last_skipped) + m];
+      }
     }
   }
 }

@@ -36,6 +36,24 @@ __device__ __forceinline__ void cgl_pack_job(const CglOpPackJob& J, long t) {
   *(gf4p)(J.dst + t * 4) = v;
 }
 
+// DataLoader(shuffle=True) over the n resident rows (capgan.py:282, 326-331): each pass is a fresh
+// keyed permutation cut into ceil(n / br) batches, the last one short (n mod br rows); local D step
+// e of round `done` takes batch done * epoch + e.  Rows past a short batch index a valid dummy row
+// (no loss, no gradient: the head's n0_dev).  Thread t of the sampler draws idx[t], t = e br + row.
+__device__ __forceinline__ void cgl_sample_at(int t, int done, int* idx, int epoch, int br, int n,
+                                              unsigned long long sseed, int* real_rows) {
+  if (t >= epoch * br) return;
+  const int e = t / br, row = t - e * br;
+  const long nb = (n + br - 1) / br;
+  const long bpos = (long)done * epoch + e;
+  const uint32_t pass = (uint32_t)(bpos / nb);
+  const long b = bpos % nb;
+  const long j = b * br + row;
+  idx[t] = (int)cgl_permute((uint32_t)(j < n ? j : n - 1), (uint32_t)n,
+                            (uint32_t)sseed ^ (pass * 0x85ebca6bu + 0x1234567u));
+  if (row == 0) real_rows[e] = (int)(n - b * br < br ? n - b * br : br);
+}
+
 __device__ __forceinline__ void cgl_round_prologue_at(int bid, int nblk, const CglBeginArgs& a, float* z, long nz,
                                                       unsigned long long zseed, int nb_norm, int* idx, int epoch,
                                                       int br, int n, unsigned long long sseed, const CglOpPack& pk) {
@@ -57,21 +75,7 @@ __device__ __forceinline__ void cgl_round_prologue_at(int bid, int nblk, const C
     cgl_normal_at((long)(bid - 1) * 256 + threadIdx.x, z, nz, zseed, (uint32_t)(done + 1), 0);
     return;
   }
-  // DataLoader(shuffle=True) over the n resident rows (capgan.py:282, 326-331): each pass is a fresh
-  // keyed permutation cut into ceil(n / br) batches, the last one short (n mod br rows); local D step
-  // e of round `done` takes batch done * epoch + e.  Rows past a short batch index a valid dummy row
-  // (no loss, no gradient: the head's n0_dev)
-  const int t = (bid - 1 - nb_norm) * 256 + threadIdx.x;
-  if (t >= epoch * br) return;
-  const int e = t / br, row = t - e * br;
-  const long nb = (n + br - 1) / br;
-  const long bpos = (long)done * epoch + e;
-  const uint32_t pass = (uint32_t)(bpos / nb);
-  const long b = bpos % nb;
-  const long j = b * br + row;
-  idx[t] = (int)cgl_permute((uint32_t)(j < n ? j : n - 1), (uint32_t)n,
-                            (uint32_t)sseed ^ (pass * 0x85ebca6bu + 0x1234567u));
-  if (row == 0) a.st->real_rows[e] = (int)(n - b * br < br ? n - b * br : br);
+  cgl_sample_at((bid - 1 - nb_norm) * 256 + (int)threadIdx.x, done, idx, epoch, br, n, sseed, a.st->real_rows);
 }
 
 #ifndef CGL_GEMM_PART_TU
@@ -83,6 +87,52 @@ __global__ __launch_bounds__(256) void cgl_pack_all(CglOpPack pk) {
   for (int q = 1; q < pk.nj; ++q)
     if (b >= pk.j[q].blk_begin) j = q;
   cgl_pack_job(pk.j[j], (long)(b - pk.j[j].blk_begin) * 256 + threadIdx.x);
+}
+
+// Co-located workers: the packing jobs of worker 0's D (pk) repeated for every worker -- blocks [w wblocks,
+// (w + 1) wblocks) pack worker w's matrices (sources pstride floats apart, packed copies at dst.d[w]).
+__global__ __launch_bounds__(256) void cgl_pack_all_grp(CglOpPack pk, int wblocks, long pstride, CglCoOff dst) {
+  const int w = blockIdx.x / wblocks, b = (int)blockIdx.x - w * wblocks;
+  int j = 0;
+  for (int q = 1; q < pk.nj; ++q)
+    if (b >= pk.j[q].blk_begin) j = q;
+  CglOpPackJob J = pk.j[j];
+  J.src += (long)w * pstride;
+  J.dst += dst.d[w];
+  cgl_pack_job(J, (long)(b - J.blk_begin) * 256 + threadIdx.x);
+}
+
+// The round prologue of a co-located context: block 0 the round's scalars (the shared server state st[0]), the
+// next nb_norm blocks the z draw, then nb_samp sampler blocks per worker -- worker w draws its own index list from
+// its own shard (sh.rows[w] rows; the stream of a one-worker context over that shard) and writes its batches' real
+// rows into st[w] -- and the packing blocks last.
+__global__ __launch_bounds__(256) void cgl_round_prologue_co(CglBeginArgs a, float* z, long nz, unsigned long long zseed,
+                                                             int nb_norm, int nb_samp, int* idx, int epoch, int br,
+                                                             unsigned long long sseed, CglCoShard sh, CglOpPack pk) {
+  const int bid = blockIdx.x, nblk = gridDim.x;
+  const int done = a.st->round;
+  const int pk0 = nblk - pk.blocks;
+  if (bid >= pk0) {
+    const int b = bid - pk0;
+    int j = 0;
+    for (int q = 1; q < pk.nj; ++q)
+      if (b >= pk.j[q].blk_begin) j = q;
+    cgl_pack_job(pk.j[j], (long)(b - pk.j[j].blk_begin) * 256 + threadIdx.x);
+    return;
+  }
+  if (bid == 0) {
+    if (threadIdx.x == 0) cgl_begin_at(a, done + 1);
+    return;
+  }
+  if (bid <= nb_norm) {
+    cgl_normal_at((long)(bid - 1) * 256 + threadIdx.x, z, nz, zseed, (uint32_t)(done + 1), 0);
+    return;
+  }
+  const int sb = bid - 1 - nb_norm;
+  const int w = sb / nb_samp;
+  if (w >= sh.nw) return;
+  cgl_sample_at((sb - w * nb_samp) * 256 + (int)threadIdx.x, done, idx + sh.idx_off[w], epoch, br, sh.rows[w], sseed,
+                (a.st + w)->real_rows);
 }
 
 // cgl_bn_apply with operand-packing jobs riding in blocks [nbn, grid) (plan_pack_carriers); blocks [0, nbn) are the
@@ -284,18 +334,28 @@ __device__ __forceinline__ void cgl_adam_tile32_at(const CglAdamArgs& a, const C
   }
 }
 
-__global__ __launch_bounds__(256) void cgl_adam_pack(CglAdamArgs a, CglAdamPack pk, CglStepState* st, int tail) {
-  __shared__ float s_img[2][2048];
-  if (cgl_adam_zblock(a, st)) return;
-  const int b = blockIdx.x;
+// block b of a cgl_adam_pack grid.  GRP (co-located workers): the packed copies lie pkoff floats past pk's
+template <bool GRP>
+__device__ __forceinline__ void cgl_adam_pack_body(const CglAdamArgs& a, const CglAdamPack& pk, CglStepState* st,
+                                                   int b, long pkoff, float* s_f, float* s_t) {
   if (b < pk.tile_blocks) {
     int j = 0;
     for (int q = 1; q < pk.nt; ++q)
       if (b >= pk.t[q].blk_begin) j = q;
-    if (pk.t[j].t32)
-      cgl_adam_tile32_at(a, pk.t[j], b - pk.t[j].blk_begin, s_img[0], s_img[1]);
-    else
-      cgl_adam_tile_at(a, pk.t[j], (long)(b - pk.t[j].blk_begin) * 256 + threadIdx.x);
+    if constexpr (GRP) {
+      CglAdamPackTile T = pk.t[j];
+      if (T.fwd) T.fwd += pkoff;
+      if (T.trn) T.trn += pkoff;
+      if (T.t32)
+        cgl_adam_tile32_at(a, T, b - T.blk_begin, s_f, s_t);
+      else
+        cgl_adam_tile_at(a, T, (long)(b - T.blk_begin) * 256 + threadIdx.x);
+    } else {
+      if (pk.t[j].t32)
+        cgl_adam_tile32_at(a, pk.t[j], b - pk.t[j].blk_begin, s_f, s_t);
+      else
+        cgl_adam_tile_at(a, pk.t[j], (long)(b - pk.t[j].blk_begin) * 256 + threadIdx.x);
+    }
   } else {
     int j = 0;
     for (int q = 1; q < pk.nr; ++q)
@@ -307,7 +367,30 @@ __global__ __launch_bounds__(256) void cgl_adam_pack(CglAdamArgs a, CglAdamPack 
       cgl_adam_at(e, st, 0, i);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void cgl_adam_pack(CglAdamArgs a, CglAdamPack pk, CglStepState* st, int tail) {
+  __shared__ float s_img[2][2048];
+  if (cgl_adam_zblock(a, st)) return;
+  const int b = blockIdx.x;
+  cgl_adam_pack_body<false>(a, pk, st, b, 0, s_img[0], s_img[1]);
   if (tail && b == 0) cgl_round_end(a, st, threadIdx.x);   // the round's end, as cgl_adam_at's first workgroup
+}
+
+// D's Adam of the W co-located workers as one launch: blocks [w wblocks, (w + 1) wblocks) are worker w's
+// cgl_adam_pack grid over its model (parameters, gradients and moments pstride floats apart in the [W][nd]
+// buffers; its packed copies at pko.d[w]); the step sizes are the shared server state's (every worker takes the
+// same local step).  Element by element the arithmetic of the one-worker launch.  No z block, no tail.
+__global__ __launch_bounds__(256) void cgl_adam_pack_grp(CglAdamArgs a, CglAdamPack pk, CglStepState* st, int wblocks,
+                                                         long pstride, CglCoOff pko) {
+  __shared__ float s_img[2][2048];
+  const int w = blockIdx.x / wblocks, b = (int)blockIdx.x - w * wblocks;
+  const long o = (long)w * pstride;
+  a.p += o;
+  a.g += o;
+  a.m += o;
+  a.v += o;
+  cgl_adam_pack_body<true>(a, pk, st, b, pko.d[w], s_img[0], s_img[1]);
 }
 
 __global__ __launch_bounds__(256) void cgl_round_prologue(CglBeginArgs a, float* z, long nz, unsigned long long zseed,

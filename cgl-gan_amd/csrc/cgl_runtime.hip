@@ -109,8 +109,17 @@ int validate(const cgl_gan_config* c) {
     if (!std::isfinite(c->loss_scale) || std::frexp(c->loss_scale, &ex) != 0.5f) return CGL_E_ARG;
     if (c->gemm_dtype == CGL_DTYPE_F32 || c->epoch != 1) return CGL_E_ARG;
   }
+  // co-located workers: the whole group in this context (rank 0 stands for it), the G-output exchange only (Mix-G's
+  // per-worker heads are not planned), no loss scaling (one found flag per model), a combinable exchange slot
+  if (c->colocated < 0) return CGL_E_ARG;
+  if (c->colocated > 1) {
+    if (c->colocated > CGL_MAX_COLOCATED || c->n_workers != c->colocated || c->rank != 0) return CGL_E_ARG;
+    if (c->exchange_layer != -1 || c->loss_scale > 0.f) return CGL_E_ARG;
+    if (((int64_t)c->batch * g.dims[g.n_layers]) % 4 != 0) return CGL_E_ARG;
+  }
   return CGL_OK;
 }
+inline int co_workers(const cgl_gan_config& c) { return c.colocated > 1 ? c.colocated : 1; }
 
 // ----------------------------------------------------------------------------------------
 // workspace carve (sizing pass with base == nullptr)
@@ -132,6 +141,19 @@ constexpr int64_t kTraceWords = CGL_GEMM_TRACE_W * CGL_GEMM_TRACE_WGS;   // CGL_
 constexpr int kMaxHeadDescs = 2 * CGL_MAX_EPOCH + 4;
 constexpr int kMaxBnDescs = 2 * CGL_MAX_LAYERS;
 constexpr int kCounters = 64;                    // head-loss tickets
+// Descriptor table and ticket sizes of a context.  One worker: the constants above (the carve every context had).
+// Co-located: worker w's D adds, per local D step, J - 1 forwards, J weight gradients and J - 1 input gradients,
+// plus 2 (J - 1) GEMMs of the G-loss pass, one head per local step and one for the G loss, each head its own ticket.
+inline int gemm_cap(const cgl_gan_config& c) {
+  const int W = co_workers(c), J = c.d.n_layers;
+  return W == 1 ? kMaxGemmDescs : 4 * CGL_MAX_LAYERS + W * (c.epoch * 3 * J + 2 * J);
+}
+inline int head_cap(const cgl_gan_config& c) {
+  return co_workers(c) == 1 ? kMaxHeadDescs : co_workers(c) * (CGL_MAX_EPOCH + 1);
+}
+inline int counter_cap(const cgl_gan_config& c) {
+  return co_workers(c) == 1 ? kCounters : co_workers(c) * (CGL_MAX_EPOCH + 1);
+}
 
 // An exchange buffer (dYL, or a Mix-G trunk gradient gdA / gG) is followed by kXchgPad floats: the gathered
 // exchange (cgl_gan_exchange_mode 1) sends [gradient | G loss | padding] as one slot of xchg_slot(n) floats.
@@ -180,6 +202,21 @@ struct WS {
   CglBnBwdDesc* bnb;
   CglBnApplyDesc* bna;
   cgl_gan_round_rec* rlog;          // the round log: CGL_ROUND_LOG_CAP records, round r in slot (r - 1) % cap
+                                    // (co-located: one ring per worker, back to back)
+  // co-located workers: wk[w] = worker w's D-side buffers (wk[0]: the fields above); st and rlog hold nw entries
+  struct Wk {
+    float* R;
+    float* P[CGL_MAX_LAYERS];
+    float* dQ[CGL_MAX_LAYERS];
+    float* dlog;
+    float* S[CGL_MAX_LAYERS];
+    float* dS[CGL_MAX_LAYERS];
+    float* hpart;
+    int* idx;
+    float* dwpk[CGL_MAX_LAYERS];
+    float* dwtpk[CGL_MAX_LAYERS];
+  } wk[CGL_MAX_COLOCATED];
+  int nw;
   int64_t total;
 };
 static_assert(sizeof(cgl_gan_round_rec) % 64 == 0, "round record: whole 64-byte lines");
@@ -192,10 +229,12 @@ WS carve_ws(const cgl_gan_config& c, void* base) {
   const cgl_mlp_spec &g = c.g, &d = c.d;
   const int L = g.n_layers, J = d.n_layers;
   const int B = c.batch, Md = c.batch_real + c.batch;
-  w.st = cv.take<CglStepState>(1);
-  w.counters = cv.take<unsigned int>(kCounters);
-  w.gemm = cv.take<CglGemmDesc>(kMaxGemmDescs);
-  w.head = cv.take<CglHeadDesc>(kMaxHeadDescs);
+  const int nw = co_workers(c);
+  w.nw = nw;
+  w.st = cv.take<CglStepState>(nw);
+  w.counters = cv.take<unsigned int>(counter_cap(c));
+  w.gemm = cv.take<CglGemmDesc>(gemm_cap(c));
+  w.head = cv.take<CglHeadDesc>(head_cap(c));
   w.bnb = cv.take<CglBnBwdDesc>(kMaxBnDescs);
   w.bna = cv.take<CglBnApplyDesc>(kMaxBnDescs);
   for (int l = 0; l < L; ++l) {
@@ -237,7 +276,40 @@ WS carve_ws(const cgl_gan_config& c, void* base) {
   }
   // the round log, after everything else (the layout of the round's own buffers is unchanged).  Not part of
   // CglStepState: that block is what a resumed run saves as raw words, and its size must not move
-  w.rlog = cv.take<cgl_gan_round_rec>(CGL_ROUND_LOG_CAP);
+  w.rlog = cv.take<cgl_gan_round_rec>((int64_t)CGL_ROUND_LOG_CAP * nw);
+  // worker 0's D-side buffers are the ones above; the other co-located workers' follow, the packed weight copies
+  // and the index list in worker 0's order (one offset per worker addresses them in the grouped launches)
+  WS::Wk& k0 = w.wk[0];
+  k0.R = w.R;
+  k0.dlog = w.dlog;
+  k0.hpart = w.hpart;
+  k0.idx = w.idx;
+  for (int j = 0; j < CGL_MAX_LAYERS; ++j) {
+    k0.P[j] = w.P[j];
+    k0.dQ[j] = w.dQ[j];
+    k0.S[j] = w.S[j];
+    k0.dS[j] = w.dS[j];
+    k0.dwpk[j] = w.dwpk[j];
+    k0.dwtpk[j] = w.dwtpk[j];
+  }
+  for (int q = 1; q < nw; ++q) {
+    WS::Wk& k = w.wk[q];
+    k.R = cv.take<float>((int64_t)Md * d.dims[0]);
+    for (int j = 0; j + 1 < J; ++j) {
+      const int f = d.dims[j + 1];
+      k.P[j] = cv.take<float>((int64_t)Md * f);
+      k.dQ[j] = cv.take<float>((int64_t)Md * f);
+      k.S[j] = cv.take<float>((int64_t)B * f);
+      k.dS[j] = cv.take<float>((int64_t)B * f);
+    }
+    k.dlog = cv.take<float>((int64_t)Md * d.dims[J]);
+    k.hpart = cv.take<float>((int64_t)((Md + kHeadRows - 1) / kHeadRows) * 2);
+    k.idx = cv.take<int>((int64_t)c.epoch * c.batch_real);
+    for (int j = 0; j + 1 < J; ++j) {
+      k.dwpk[j] = cv.take<float>(cgl_pk_floats(d.dims[j + 1], d.dims[j]));
+      k.dwtpk[j] = cv.take<float>(cgl_pk_floats(d.dims[j], d.dims[j + 1]));
+    }
+  }
   w.total = cv.off;
   return w;
 }
@@ -267,6 +339,8 @@ struct Launch {
   int layer = -1;           // K_BNAPPLY: the G layer whose forward GEMM reads this launch's output
   int pk = -1;              // K_BNAPPLY: index of the packing jobs it carries (cgl_gan.carry), -1: none
   int pf_first = -1, pf_count = 0;   // K_GEMM: the next GEMM launch's descriptor range (link_gemm_prefetch)
+  int nw = 1;               // co-located workers sharing the launch (K_GEMM: count = nw x problems per worker,
+                            // cgl_gemm_grp; K_HEAD: count = nw heads; K_ADAM adpk: nw grids of grid_y blocks)
 };
 
 // Every kernel of a plan is launched through klaunch.  Normally a plain launch; while cgl_gan_profile
@@ -288,7 +362,8 @@ hipError_t gemm_lds_attr() {
   static bool done = false;
   if (!done) {
     // advisory on this platform (launches up to the per-CU LDS succeed); never fail on it
-    for (const void* fn : {(const void*)cgl_gemm_f32<1, 1>, (const void*)cgl_gemm_f32<2, 2>}) {
+    for (const void* fn : {(const void*)cgl_gemm_f32<1, 1>, (const void*)cgl_gemm_f32<2, 2>,
+                           (const void*)cgl_gemm_grp<1, 1>, (const void*)cgl_gemm_grp<2, 2>}) {
       for (int kb : {150, 128, 96, 64}) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kb * 1024);
         (void)hipGetLastError();
@@ -327,6 +402,24 @@ void launch_gemm(int blk, int grid, int shmem, hipStream_t s, const CglGemmDesc*
     launch_gemm_dt<CGL_DTYPE_BF16>(blk, grid, shmem, s, d, n);
   else
     launch_gemm_dt<CGL_DTYPE_F32>(blk, grid, shmem, s, d, n);
+}
+
+// The grouped launch of co-located workers (cgl_gemm_grp): d = [nw][q] descriptors, n = the selection of one worker's q
+template <int DT>
+void launch_gemm_grp_dt(int blk, int grid, int shmem, hipStream_t s, const CglGemmDesc* d, int nw, int q, CglGemmSel n) {
+  if (blk == 2)
+    klaunch(cgl_gemm_grp<2, 2, DT>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, grid / nw, q, n.wg1, n.wg2, n.meta, n.pf, n.pf_lines);
+  else
+    klaunch(cgl_gemm_grp<1, 1, DT>, dim3(grid), dim3(CGL_GEMM_THREADS), shmem, s, d, grid / nw, q, n.wg1, n.wg2, n.meta, n.pf, n.pf_lines);
+}
+void launch_gemm_grp(int blk, int grid, int shmem, hipStream_t s, const CglGemmDesc* d, int nw, int q, CglGemmSel n,
+                     int dt) {
+  if (dt == CGL_DTYPE_F16)
+    launch_gemm_grp_dt<CGL_DTYPE_F16>(blk, grid, shmem, s, d, nw, q, n);
+  else if (dt == CGL_DTYPE_BF16)
+    launch_gemm_grp_dt<CGL_DTYPE_BF16>(blk, grid, shmem, s, d, nw, q, n);
+  else
+    launch_gemm_grp_dt<CGL_DTYPE_F32>(blk, grid, shmem, s, d, nw, q, n);
 }
 
 // Cost model of one GEMM launch (cycles) used to pick the wave arrangement WM x WN x WK and
@@ -438,6 +531,7 @@ struct cgl_gan {
   CglOpPack pack{};          // the round prologue's operand-packing jobs (none when pack_adam)
   CglOpPack pack_all{};      // every packing job of the plan (cgl_gan_sync_params)
   CglOpPack pack_d{};        // D's packing jobs alone (cgl_gan_sync_params_d)
+  CglOpPack pack_g{};        // G's alone (co-located: D's are repeated per worker, launch_pack_sync)
   bool pack_adam = false;    // G's packed weights written by the G Adam launch (cgl_adam_pack), not the prologue
   bool z_ahead = false;      // z drawn one round ahead by the G Adam launch into ws.znext (plan_z_ahead)
   CglAdamPack adam_pack{};
@@ -453,6 +547,13 @@ struct cgl_gan {
   int xmode = 0;                     // cgl_gan_exchange_mode: 0 reduce (alpha_scale + all-reduce), 1 gathered
   int ghead = -1;                    // the G-loss head descriptor (its loss_out2 = the exchange slot's loss word)
   std::vector<Launch> phBhead;       // phase B's head under xmode 1: cgl_alpha_combine
+  // co-located workers (cfg.colocated = nw >= 2; else nw = 1)
+  int nw = 1;
+  int64_t nd = 0;                    // floats of one D model (the stride of the [nw][nd] buffers)
+  CglCoOff dpk_off{};                // worker w's packed D copies, in floats from worker 0's
+  CglCoShard shard{};                // the sampler's shards
+  int64_t shard_row0[CGL_MAX_COLOCATED] = {};
+  int plan_err = 0;                  // a grouped launch whose W copies are not the same problem
   // parameter tensor pointers
   std::vector<TensorRec> gl, dl;
   int64_t run_mean_off[CGL_MAX_LAYERS], run_var_off[CGL_MAX_LAYERS];
@@ -478,14 +579,15 @@ float* ggrad(const cgl_gan* c, int layer, int kind) {
     if (t.layer == layer && t.kind == kind) return c->bufs.g_grads + t.off;
   return nullptr;
 }
-const float* dparam(const cgl_gan* c, int layer, int kind) {
+// (wk: the co-located worker whose model, nd floats after the previous worker's)
+const float* dparam(const cgl_gan* c, int layer, int kind, int wk = 0) {
   for (auto& t : c->dl)
-    if (t.layer == layer && t.kind == kind) return c->bufs.d_params + t.off;
+    if (t.layer == layer && t.kind == kind) return c->bufs.d_params + wk * c->nd + t.off;
   return nullptr;
 }
-float* dgrad(const cgl_gan* c, int layer, int kind) {
+float* dgrad(const cgl_gan* c, int layer, int kind, int wk = 0) {
   for (auto& t : c->dl)
-    if (t.layer == layer && t.kind == kind) return c->bufs.d_grads + t.off;
+    if (t.layer == layer && t.kind == kind) return c->bufs.d_grads + wk * c->nd + t.off;
   return nullptr;
 }
 
@@ -555,10 +657,13 @@ bool gemm_tile_pick(const CglGemmDesc& d, int* o) {
   return false;
 }
 
-// Add a grouped GEMM launch built from `descs` (workgroup offsets assigned here).
-void push_gemm(cgl_gan* c, std::vector<Launch>& ph, std::vector<CglGemmDesc> descs) {
+// Add a grouped GEMM launch built from `descs` (workgroup offsets assigned here).  nw > 1: descs = [nw][q], the
+// same q problems for each co-located worker (cgl_gemm_grp) -- every choice below depends on a problem's shape and
+// on the largest problem of the group only, so a worker's tiles are those of its own launch of the q problems.
+void push_gemm(cgl_gan* c, std::vector<Launch>& ph, std::vector<CglGemmDesc> descs, int nw = 1) {
   Launch L;
   L.kind = K_GEMM;
+  L.nw = nw;
   L.first = (int)c->gemm.size();
   L.count = (int)descs.size();
   int wg = 0, stage = 0;
@@ -601,6 +706,16 @@ void push_gemm(cgl_gan* c, std::vector<Launch>& ph, std::vector<CglGemmDesc> des
   }
   L.grid = wg;
   L.shmem = stage;
+  if (nw > 1) {     // the W copies must be one problem: same selection, same workgroups
+    const int q = L.count / nw;
+    if (q < 1 || q > 3 || q * nw != L.count || wg % nw) c->plan_err = CGL_E_ARG;
+    for (int i = q; i < L.count && !c->plan_err; ++i) {
+      const CglGemmDesc &a = c->gemm[L.first + i], &b = c->gemm[L.first + i % q];
+      if (a.layout != b.layout || (a.a_vec && a.b_vec) != (b.a_vec && b.b_vec) || a.tiles_m != b.tiles_m ||
+          a.tiles_n != b.tiles_n || a.wg_begin != b.wg_begin + (i / q) * (wg / nw))
+        c->plan_err = CGL_E_ARG;
+    }
+  }
   if (getenv("CGL_PLAN_DEBUG")) {
     for (int q = L.first; q < L.first + L.count; ++q) {
       const CglGemmDesc& d = c->gemm[q];
@@ -619,6 +734,19 @@ void push_head(cgl_gan* c, std::vector<Launch>& ph, const CglHeadDesc& h) {
   L.count = 1;
   L.grid = (h.M + kHeadRows - 1) / kHeadRows;
   c->head.push_back(h);
+  ph.push_back(L);
+}
+
+// the same head for every co-located worker as one launch (cgl_head_loss_grp): hs[w] = worker w's descriptor
+void push_head_grp(cgl_gan* c, std::vector<Launch>& ph, const std::vector<CglHeadDesc>& hs) {
+  Launch L;
+  L.kind = K_HEAD;
+  L.first = (int)c->head.size();
+  L.count = (int)hs.size();
+  L.nw = L.count;
+  L.grid_y = (hs[0].M + kHeadRows - 1) / kHeadRows;    // workgroups per worker
+  L.grid = L.grid_y * L.count;
+  for (auto& h : hs) c->head.push_back(h);
   ph.push_back(L);
 }
 
@@ -690,6 +818,7 @@ void fuse_wgrad_adam(cgl_gan* c, std::vector<Launch>& ph, int model) {
   const cgl_gan_config& cf = c->cfg;
   const cgl_mlp_spec& sp = model == CGL_MODEL_G ? cf.g : cf.d;
   if (!env || cf.loss_scale > 0.f || cf.gemm_dtype != CGL_DTYPE_F32 || sp.bn[0] || ph.size() < 2) return;
+  if (c->nw > 1) return;    // (co-located: one Adam launch over the W models, not carried by a GEMM)
   Launch& G = ph[ph.size() - 2];
   Launch& A = ph.back();
   if (G.kind != K_GEMM || G.count != 1 || A.kind != K_ADAM) return;
@@ -744,7 +873,7 @@ void fuse_wgrad_adam(cgl_gan* c, std::vector<Launch>& ph, int model) {
 // partials visible; nothing in the GEMM launch reads the losses.  CGL_HEAD_DEFER=0 keeps the ticket path.
 void defer_heads(cgl_gan* c) {
   const int env = getenv("CGL_HEAD_DEFER") ? atoi(getenv("CGL_HEAD_DEFER")) : 1;   // read per plan
-  if (!env) return;
+  if (!env || c->nw > 1) return;     // (co-located: W heads per launch, one finisher slot -- the ticket path)
   for (std::vector<Launch>* ph : {&c->phA, &c->phB}) {
     for (size_t i = 0; i + 1 < ph->size(); ++i) {
       Launch& H = (*ph)[i];
@@ -768,7 +897,8 @@ void defer_heads(cgl_gan* c) {
 void fuse_prologue(cgl_gan* c) {
   const int env = getenv("CGL_FUSE_PRO") ? atoi(getenv("CGL_FUSE_PRO")) : 1;
   std::vector<Launch>& A = c->phA;
-  if (!env || c->cfg.gemm_dtype != CGL_DTYPE_F32 || A.size() < 2) return;
+  // (co-located: the prologue samples W shards, cgl_round_prologue_co -- two launches)
+  if (!env || c->cfg.gemm_dtype != CGL_DTYPE_F32 || A.size() < 2 || c->nw > 1) return;
   const Launch& P = A[0];
   const Launch& G = A[1];
   if (P.kind != K_PROLOGUE || G.kind != K_GEMM || G.count != 1) return;
@@ -983,18 +1113,18 @@ bool plan_d_pack(cgl_gan* c) {
   return c->d_pack;
 }
 // the packed copy of D layer j, or null (the forward GEMM reads V_j row-major)
-const float* d_packed(cgl_gan* c, int j, int trans = 0) {
+const float* d_packed(cgl_gan* c, int j, int trans = 0, int wk = 0) {
   if (!c->d_pack) return nullptr;
   for (auto& J : c->d_jobs)
-    if (J.src == dparam(c, j, 0) && J.trans == trans) return J.dst;
+    if (J.src == dparam(c, j, 0) && J.trans == trans) return J.dst + c->dpk_off.d[wk];
   return nullptr;
 }
 // The input gradient dX = dY V_j of D layer j ([rows][fo] x [fo][fi]): NT on the packed transpose P(V_j^T) kept by
 // D's Adam, or NN on the row-major V_j.  The caller sets the epilogue.
-CglGemmDesc d_input_grad(cgl_gan* c, int j, int rows_, const float* dY) {
+CglGemmDesc d_input_grad(cgl_gan* c, int j, int rows_, const float* dY, int wk = 0) {
   const cgl_mlp_spec& d = c->cfg.d;
   const int fi = d.dims[j], fo = d.dims[j + 1];
-  const float* pkt = d_packed(c, j, 1);
+  const float* pkt = d_packed(c, j, 1, wk);
   CglGemmDesc n = make_gemm(pkt ? 0 : 1, rows_, fi, fo);
   n.a = rows(dY, fo);
   n.a_vec = (fo % 4 == 0);
@@ -1004,7 +1134,7 @@ CglGemmDesc d_input_grad(cgl_gan* c, int j, int rows_, const float* dY) {
     n.b_vec = 1;
     choose_tiles(n);
   } else {
-    n.b = rows(dparam(c, j, 0), fi);
+    n.b = rows(dparam(c, j, 0, wk), fi);
   }
   return n;
 }
@@ -1074,10 +1204,10 @@ int build_plan(cgl_gan* c) {
       Lp.nb_norm = (int)((Lp.nn / 4 + 255) / 256);
     }
     if (cf.sample_n > 0) {
-      Lp.nb_samp = (cf.epoch * Br + 255) / 256;
+      Lp.nb_samp = (cf.epoch * Br + 255) / 256;       // (co-located: per worker)
       real_idx = w.idx;
     }
-    Lp.grid = 1 + Lp.nb_norm + Lp.nb_samp;
+    Lp.grid = 1 + Lp.nb_norm + Lp.nb_samp * c->nw;
     A.push_back(Lp);
   }
 
@@ -1176,86 +1306,112 @@ int build_plan(cgl_gan* c) {
   const float* Xg = w.gout[L - 1] + (int64_t)B * img;
 
   // ---- local D steps (Worker.train capgan.py:324-341)
+  // Co-located workers (NW > 1): every stage below is ONE launch holding the NW workers' copies of it -- worker q's
+  // descriptors read its own model (dparam(.., q)), real rows and buffers (w.wk[q]) and the shared G output.
+  const int NW = c->nw;
   const int C = d.dims[J];
   const float combine = cf.loss == CGL_LOSS_CE2 ? 0.5f : 1.0f;
+  // the real rows of worker q's local step ep: through the sampler's / the caller's index list, or in order
+  const int64_t eb = (int64_t)cf.epoch * Br;
+  auto real_src = [&](int q, int ep, int fi) {
+    CglRowSrc r;
+    std::memset(&r, 0, sizeof(r));
+    r.ld = fi;
+    if (cf.sample_n > 0) {          // the worker's own shard and index list
+      r.p0 = c->bufs.real + c->shard_row0[q] * fi;
+      r.idx0 = w.wk[q].idx + (int64_t)ep * Br;
+    } else if (real_idx) {          // the caller's indices (into the whole of `real`)
+      r.p0 = c->bufs.real;
+      r.idx0 = real_idx + q * eb + (int64_t)ep * Br;
+    } else {
+      r.p0 = c->bufs.real + (q * eb + (int64_t)ep * Br) * fi;
+    }
+    return r;
+  };
   // hidden-layer forwards of the D-step input rows: the real rows (through the sampler's index list) and
   // the Xd rows as one 2-segment GEMM
   plan_d_pack(c);
+  for (int q = 1; q < NW; ++q) c->dpk_off.d[q] = w.wk[q].dwpk[0] - w.wk[0].dwpk[0];
   auto d_forward = [&](int ep) {
     for (int j = 0; j + 1 < J; ++j) {
       const int fi = d.dims[j], fo = d.dims[j + 1];
-      CglGemmDesc e = make_gemm(0, Md, fo, fi);
-      if (j == 0) {
-        CglRowSrc r;
-        std::memset(&r, 0, sizeof(r));
-        r.split = 0x7fffffff;
-        r.ld = fi;
-        if (real_idx) {
-          r.p0 = c->bufs.real;
-          r.idx0 = real_idx + (int64_t)ep * Br;
+      std::vector<CglGemmDesc> grp;
+      for (int q = 0; q < NW; ++q) {
+        const WS::Wk& k = w.wk[q];
+        CglGemmDesc e = make_gemm(0, Md, fo, fi);
+        if (j == 0) {
+          CglRowSrc r = real_src(q, ep, fi);
+          r.p1 = Xd;
+          r.split = Br;
+          e.a = r;
+          e.a_vec = (fi % 4 == 0) && al16(r.p0) && al16(Xd);
+          e.a_copy = k.R;
+          e.a_copy_ld = fi;
+          e.a_copy_row0 = 0;
         } else {
-          r.p0 = c->bufs.real + (int64_t)ep * Br * fi;
+          e.a = rows(k.P[j - 1], fi);
+          e.a_vec = (fi % 4 == 0);
         }
-        r.p1 = Xd;
-        r.split = Br;
-        e.a = r;
-        e.a_vec = (fi % 4 == 0) && al16(c->bufs.real) && al16(Xd);
-        e.a_copy = w.R;
-        e.a_copy_ld = fi;
-        e.a_copy_row0 = 0;
-      } else {
-        e.a = rows(w.P[j - 1], fi);
-        e.a_vec = (fi % 4 == 0);
+        e.b = rows(dparam(c, j, 0, q), fi);
+        e.b_vec = (fi % 4 == 0);
+        if (const float* pkd = d_packed(c, j, 0, q)) {
+          e.b = rows(pkd, fi);
+          e.b_pk = 1;
+          e.b_vec = 1;
+          choose_tiles(e);
+        }
+        e.bias = dparam(c, j, 1, q);
+        e.act = CGL_EPI_ACT_LEAKY;
+        e.slope = sl;
+        e.C = k.P[j];
+        e.ldc = fo;
+        grp.push_back(e);
       }
-      e.b = rows(dparam(c, j, 0), fi);
-      e.b_vec = (fi % 4 == 0);
-      if (const float* pkd = d_packed(c, j)) {
-        e.b = rows(pkd, fi);
-        e.b_pk = 1;
-        e.b_vec = 1;
-        choose_tiles(e);
-      }
-      e.bias = dparam(c, j, 1);
-      e.act = CGL_EPI_ACT_LEAKY;
-      e.slope = sl;
-      e.C = w.P[j];
-      e.ldc = fo;
-      push_gemm(c, A, {e});
+      push_gemm(c, A, grp, NW);
     }
   };
   // the loss head: CE/BCE on the logits, dlogits and the gradient into the last
   // hidden layer; real rows are segment 0 (target valid), Xd rows segment 1 (target fake)
   auto d_head = [&](int ep) {
     const int F = d.dims[J - 1];
-    CglHeadDesc h;
-    std::memset(&h, 0, sizeof(h));
-    h.M = Md;
-    h.F = F;
-    h.C = C;
-    h.loss = cf.loss;
-    h.P = w.P[J - 2];
-    h.ldp = F;
-    h.W = dparam(c, J - 1, 0);
-    h.b = dparam(c, J - 1, 1);
-    h.split = Br;
-    h.t0 = 1;
-    h.t1 = 0;
-    h.w0 = combine / Br;
-    h.w1 = combine / B;
-    h.dlogits = w.dlog;
-    h.dP = w.dQ[J - 2];
-    h.lddp = F;
-    h.slope = sl;
-    h.part = w.hpart;
-    h.counter = w.counters + ep;
-    if (cf.sample_n > 0) h.n0_dev = &st->real_rows[ep];   // the sampler's short batch
-    h.loss_out0 = &st->d_loss_parts[ep][0];
-    h.loss_out1 = &st->d_loss_parts[ep][1];
-    h.combine = combine;
-    h.combine_out = &st->d_loss[ep];
-    h.scale_dev = scaling ? &st->scale[0] : nullptr;
-    h.rows_per_wg = kHeadRows;
-    push_head(c, A, h);
+    std::vector<CglHeadDesc> hs;
+    for (int q = 0; q < NW; ++q) {
+      const WS::Wk& k = w.wk[q];
+      CglStepState* sq = st + q;       // worker q's round scalars (q = 0: the server state itself)
+      CglHeadDesc h;
+      std::memset(&h, 0, sizeof(h));
+      h.M = Md;
+      h.F = F;
+      h.C = C;
+      h.loss = cf.loss;
+      h.P = k.P[J - 2];
+      h.ldp = F;
+      h.W = dparam(c, J - 1, 0, q);
+      h.b = dparam(c, J - 1, 1, q);
+      h.split = Br;
+      h.t0 = 1;
+      h.t1 = 0;
+      h.w0 = combine / Br;
+      h.w1 = combine / B;
+      h.dlogits = k.dlog;
+      h.dP = k.dQ[J - 2];
+      h.lddp = F;
+      h.slope = sl;
+      h.part = k.hpart;
+      h.counter = w.counters + q * (CGL_MAX_EPOCH + 1) + ep;
+      if (cf.sample_n > 0) h.n0_dev = &sq->real_rows[ep];   // the sampler's short batch
+      h.loss_out0 = &sq->d_loss_parts[ep][0];
+      h.loss_out1 = &sq->d_loss_parts[ep][1];
+      h.combine = combine;
+      h.combine_out = &sq->d_loss[ep];
+      h.scale_dev = scaling ? &st->scale[0] : nullptr;
+      h.rows_per_wg = kHeadRows;
+      hs.push_back(h);
+    }
+    if (NW == 1)
+      push_head(c, A, hs[0]);
+    else
+      push_head_grp(c, A, hs);
   };
   for (int ep = 0; ep < cf.epoch; ++ep) {
     d_forward(ep);
@@ -1263,45 +1419,52 @@ int build_plan(cgl_gan* c) {
     // backward: weight grads (TN, + bias column) and input grads (NN, LeakyReLU' mask)
     for (int j = J - 1; j >= 0; --j) {
       std::vector<CglGemmDesc> grp;
-      if (j == J - 1) {
-        // grad of the output layer: dlogits^T . P[J-2]
-        CglGemmDesc t = make_gemm(2, C, d.dims[J - 1] + 1, Md);
-        t.a = rows(w.dlog, C);
-        t.b = rows(w.P[J - 2], d.dims[J - 1]);
-        t.b_ones_col = 1;
-        t.C = dgrad(c, J - 1, 0);
-        t.ldc = d.dims[J - 1];
-        t.bias_out = dgrad(c, J - 1, 1);
-        if (scaling) t.inf_flag = &st->found[0];
-        grp.push_back(t);
-        --j;  // the layer below is handled in the same launch
+      const int jtop = j;
+      for (int q = 0; q < NW; ++q) {
+        const WS::Wk& k = w.wk[q];
+        j = jtop;
+        if (j == J - 1) {
+          // grad of the output layer: dlogits^T . P[J-2]
+          CglGemmDesc t = make_gemm(2, C, d.dims[J - 1] + 1, Md);
+          t.a = rows(k.dlog, C);
+          t.b = rows(k.P[J - 2], d.dims[J - 1]);
+          t.b_ones_col = 1;
+          t.C = dgrad(c, J - 1, 0, q);
+          t.ldc = d.dims[J - 1];
+          t.bias_out = dgrad(c, J - 1, 1, q);
+          if (scaling) t.inf_flag = &st->found[0];
+          grp.push_back(t);
+          --j;  // the layer below is handled in the same launch
+        }
+        {
+          const float* in = (j >= 1) ? k.P[j - 1] : k.R;
+          CglGemmDesc t = make_gemm(2, d.dims[j + 1], d.dims[j] + 1, Md);
+          t.a = rows(k.dQ[j], d.dims[j + 1]);
+          t.b = rows(in, d.dims[j]);
+          t.b_ones_col = 1;
+          t.C = dgrad(c, j, 0, q);
+          t.ldc = d.dims[j];
+          t.bias_out = dgrad(c, j, 1, q);
+          if (scaling) t.inf_flag = &st->found[0];
+          grp.push_back(t);
+        }
+        if (j >= 1) {
+          CglGemmDesc n = d_input_grad(c, j, Md, k.dQ[j], q);
+          n.mask_ref = k.P[j - 1];
+          n.mask_ld = d.dims[j];
+          n.slope = sl;
+          n.C = k.dQ[j - 1];
+          n.ldc = d.dims[j];
+          grp.push_back(n);
+        }
       }
-      {
-        const float* in = (j >= 1) ? w.P[j - 1] : w.R;
-        CglGemmDesc t = make_gemm(2, d.dims[j + 1], d.dims[j] + 1, Md);
-        t.a = rows(w.dQ[j], d.dims[j + 1]);
-        t.b = rows(in, d.dims[j]);
-        t.b_ones_col = 1;
-        t.C = dgrad(c, j, 0);
-        t.ldc = d.dims[j];
-        t.bias_out = dgrad(c, j, 1);
-        if (scaling) t.inf_flag = &st->found[0];
-        grp.push_back(t);
-      }
-      if (j >= 1) {
-        CglGemmDesc n = d_input_grad(c, j, Md, w.dQ[j]);
-        n.mask_ref = w.P[j - 1];
-        n.mask_ld = d.dims[j];
-        n.slope = sl;
-        n.C = w.dQ[j - 1];
-        n.ldc = d.dims[j];
-        grp.push_back(n);
-      }
-      push_gemm(c, A, grp);
+      push_gemm(c, A, grp, NW);
     }
     int64_t nd = 0;
     param_layout(d, &nd);
-    push_adam(c, A, c->bufs.d_params, c->bufs.d_grads, c->bufs.d_m, c->bufs.d_v, (long)nd,
+    // D's Adam: one launch over the NW models.  Without packed copies the [NW][nd] block is one flat buffer (every
+    // worker takes the same step); with them, NW grids of cgl_adam_pack (cgl_adam_pack_grp)
+    push_adam(c, A, c->bufs.d_params, c->bufs.d_grads, c->bufs.d_m, c->bufs.d_v, (long)(c->d_pack ? nd : nd * NW),
               &st->d_step_size[ep], &st->d_bc2sqrt[ep], 0, scaling ? &st->scale[0] : nullptr,
               scaling ? &st->found[0] : nullptr);
     if (c->d_pack) {    // D's Adam keeps the packed copies (the D forwards after it read them)
@@ -1309,75 +1472,103 @@ int build_plan(cgl_gan* c) {
                            c->adam_pack_d))
         return CGL_E_STATE;   // (plan_d_pack admitted only matrices build_adam_pack accepts)
       A.back().apk_d = 1;
+      if (NW > 1) {
+        Launch& Ad = A.back();
+        Ad.nw = NW;
+        Ad.grid_y = Ad.grid;      // blocks per worker
+        Ad.grid = Ad.grid_y * NW;
+      }
     }
     fuse_wgrad_adam(c, A, CGL_MODEL_D);
   }
 
   // ---- G loss through the updated D (capgan.py:343-347) and its input gradient
+  // (co-located: worker q's final input gradient goes straight into slot q of the gathered exchange buffer, its G
+  // loss into the word after it -- [gradient | G loss | pad], the layout of exchange mode 1)
+  const int64_t xslot = xchg_slot((int64_t)B * img);
   for (int j = 0; j + 1 < J; ++j) {
     const int fi = d.dims[j], fo = d.dims[j + 1];
-    CglGemmDesc e = make_gemm(0, B, fo, fi);
-    e.a = rows(j == 0 ? Xg : w.S[j - 1], fi);
-    e.a_vec = (fi % 4 == 0);
-    e.b = rows(dparam(c, j, 0), fi);
-    e.b_vec = (fi % 4 == 0);
-    if (const float* pkd = d_packed(c, j)) {
-      e.b = rows(pkd, fi);
-      e.b_pk = 1;
-      e.b_vec = 1;
-      choose_tiles(e);
+    std::vector<CglGemmDesc> grp;
+    for (int q = 0; q < NW; ++q) {
+      const WS::Wk& k = w.wk[q];
+      CglGemmDesc e = make_gemm(0, B, fo, fi);
+      e.a = rows(j == 0 ? Xg : k.S[j - 1], fi);
+      e.a_vec = (fi % 4 == 0);
+      e.b = rows(dparam(c, j, 0, q), fi);
+      e.b_vec = (fi % 4 == 0);
+      if (const float* pkd = d_packed(c, j, 0, q)) {
+        e.b = rows(pkd, fi);
+        e.b_pk = 1;
+        e.b_vec = 1;
+        choose_tiles(e);
+      }
+      e.bias = dparam(c, j, 1, q);
+      e.act = CGL_EPI_ACT_LEAKY;
+      e.slope = sl;
+      e.C = k.S[j];
+      e.ldc = fo;
+      grp.push_back(e);
     }
-    e.bias = dparam(c, j, 1);
-    e.act = CGL_EPI_ACT_LEAKY;
-    e.slope = sl;
-    e.C = w.S[j];
-    e.ldc = fo;
-    push_gemm(c, A, {e});
+    push_gemm(c, A, grp, NW);
   }
   {
-    CglHeadDesc h;
-    std::memset(&h, 0, sizeof(h));
-    h.M = B;
-    h.F = d.dims[J - 1];
-    h.C = C;
-    h.loss = cf.loss;
-    h.P = w.S[J - 2];
-    h.ldp = d.dims[J - 1];
-    h.W = dparam(c, J - 1, 0);
-    h.b = dparam(c, J - 1, 1);
-    h.split = B;
-    h.t0 = 1;
-    h.t1 = 1;
-    h.w0 = 1.0f / B;
-    h.w1 = 1.0f / B;
-    h.dP = w.dS[J - 2];
-    h.lddp = d.dims[J - 1];
-    h.slope = sl;
-    h.part = w.hpart;
-    h.counter = w.counters + CGL_MAX_EPOCH;
-    h.loss_out0 = &st->g_loss_parts[0];
+    std::vector<CglHeadDesc> hs;
+    for (int q = 0; q < NW; ++q) {
+      const WS::Wk& k = w.wk[q];
+      CglHeadDesc h;
+      std::memset(&h, 0, sizeof(h));
+      h.M = B;
+      h.F = d.dims[J - 1];
+      h.C = C;
+      h.loss = cf.loss;
+      h.P = k.S[J - 2];
+      h.ldp = d.dims[J - 1];
+      h.W = dparam(c, J - 1, 0, q);
+      h.b = dparam(c, J - 1, 1, q);
+      h.split = B;
+      h.t0 = 1;
+      h.t1 = 1;
+      h.w0 = 1.0f / B;
+      h.w1 = 1.0f / B;
+      h.dP = k.dS[J - 2];
+      h.lddp = d.dims[J - 1];
+      h.slope = sl;
+      h.part = k.hpart;
+      h.counter = w.counters + q * (CGL_MAX_EPOCH + 1) + CGL_MAX_EPOCH;
+      h.loss_out0 = &(st + q)->g_loss_parts[0];
+      if (NW > 1) h.loss_out2 = w.gath + q * xslot + (int64_t)B * img;
+      h.combine = 1.0f;
+      h.scale_dev = scaling ? &st->scale[1] : nullptr;
+      h.rows_per_wg = kHeadRows;
+      hs.push_back(h);
+    }
     c->ghead = (int)c->head.size();
-    h.combine = 1.0f;
-    h.scale_dev = scaling ? &st->scale[1] : nullptr;
-    h.rows_per_wg = kHeadRows;
-    push_head(c, A, h);
+    if (NW == 1)
+      push_head(c, A, hs[0]);
+    else
+      push_head_grp(c, A, hs);
   }
   for (int j = J - 2; j >= 0; --j) {
     // dS[j-1] = (dS[j] V_j) * leaky'(S[j-1]);  j == 0: dXg = dS[0] V_0, then Tanh'
-    CglGemmDesc n = d_input_grad(c, j, B, w.dS[j]);
-    n.slope = sl;
-    if (j >= 1) {
-      n.mask_ref = w.S[j - 1];
-      n.mask_ld = d.dims[j];
-      n.C = w.dS[j - 1];
-      n.ldc = d.dims[j];
-    } else {
-      n.tanh_ref = Xg;
-      n.tanh_ld = img;
-      n.C = w.dYL;
-      n.ldc = img;
+    std::vector<CglGemmDesc> grp;
+    for (int q = 0; q < NW; ++q) {
+      const WS::Wk& k = w.wk[q];
+      CglGemmDesc n = d_input_grad(c, j, B, k.dS[j], q);
+      n.slope = sl;
+      if (j >= 1) {
+        n.mask_ref = k.S[j - 1];
+        n.mask_ld = d.dims[j];
+        n.C = k.dS[j - 1];
+        n.ldc = d.dims[j];
+      } else {
+        n.tanh_ref = Xg;
+        n.tanh_ld = img;
+        n.C = NW > 1 ? w.gath + q * xslot : w.dYL;
+        n.ldc = img;
+      }
+      grp.push_back(n);
     }
-    push_gemm(c, A, {n});
+    push_gemm(c, A, grp, NW);
   }
 
   // ---- G backward (Server.train: F_max.backward() capgan.py:258, on the Xg rows)
@@ -1386,6 +1577,12 @@ int build_plan(cgl_gan* c) {
     c->xchg = w.dYL;
     c->xchg_n = (int64_t)B * img;
     ph = &Bp;
+  }
+  if (NW > 1) {     // the local exchange: alpha from the NW losses, dYL = sum_q alpha_q g_q in rank order
+    Launch Lc;
+    Lc.kind = K_COMBINE;
+    Lc.grid = (int)std::min<int64_t>((c->xchg_n / 4 + 255) / 256, 1024);
+    Bp.push_back(Lc);
   }
   // The BatchNorm1d backward of layer l - 1 (with the LeakyReLU' mask of its output) is a cgl_bn_bwd launch
   // between layer l's input-gradient GEMM and layer l - 1's GEMMs.
@@ -1487,6 +1684,7 @@ int build_plan(cgl_gan* c) {
   push_adam(c, *ph, c->bufs.g_params, c->bufs.g_grads, c->bufs.g_m, c->bufs.g_v, (long)ng, &st->g_step_size,
             &st->g_bc2sqrt, 1, scaling ? &st->scale[1] : nullptr, scaling ? &st->found[1] : nullptr);
   ph->back().adam.log = w.rlog;   // the round's tail launch writes the round's record
+  ph->back().adam.nw = NW > 1 ? NW : 0;
   if (c->z_ahead) {
     Launch& Ag = ph->back();
     Ag.adam.znext = w.znext;
@@ -1507,6 +1705,7 @@ int build_plan(cgl_gan* c) {
     }
     c->pack.blocks = blk;
     c->pack_all = c->pack;
+    c->pack_g = c->pack;
     std::memset(&c->pack_d, 0, sizeof(c->pack_d));
     for (auto& J : c->d_jobs) {        // D's packed copies too (sync_params / reset: D written from outside)
       if (c->pack_all.nj == CGL_PACK_MAXJ || c->pack_d.nj == CGL_PACK_MAXJ) return CGL_E_SIZE;
@@ -1533,10 +1732,10 @@ int build_plan(cgl_gan* c) {
   }
   fuse_prologue(c);
   link_gemm_prefetch(c);
-  if ((int)c->gemm.size() > kMaxGemmDescs || (int)c->head.size() > kMaxHeadDescs ||
+  if ((int)c->gemm.size() > gemm_cap(cf) || (int)c->head.size() > head_cap(cf) ||
       (int)c->bnb.size() > kMaxBnDescs || (int)c->bna.size() > kMaxBnDescs)
     return CGL_E_SIZE;
-  return CGL_OK;
+  return c->plan_err;
 }
 
 
@@ -1555,17 +1754,22 @@ CglGemmSel gemm_prefetch(const cgl_gan* c, const Launch& L) {
 int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s) {
   switch (L.kind) {
     case K_GEMM:
-      if (L.count > 3) return CGL_E_SIZE;
+      if (L.count > 3 * L.nw) return CGL_E_SIZE;
     {
-      CglGemmSel q = gemm_sel(c->gemm.data() + L.first, L.count);
+      CglGemmSel q = gemm_sel(c->gemm.data() + L.first, L.count / L.nw);
       const CglGemmSel pq = gemm_prefetch(c, L);
       q.pf = pq.pf;
       q.pf_lines = pq.pf_lines;
-      launch_gemm(L.blk, L.grid, L.shmem, s, c->ws.gemm + L.first, q, L.dt);
+      if (L.nw > 1)
+        launch_gemm_grp(L.blk, L.grid, L.shmem, s, c->ws.gemm + L.first, L.nw, L.count / L.nw, q, L.dt);
+      else
+        launch_gemm(L.blk, L.grid, L.shmem, s, c->ws.gemm + L.first, q, L.dt);
       break;
     }
     case K_HEAD:
-      if (L.pk >= 0)
+      if (L.nw > 1)
+        klaunch(cgl_head_loss_grp, dim3(L.grid), dim3(256), 0, s, (const CglHeadDesc*)(c->ws.head + L.first), L.grid_y);
+      else if (L.pk >= 0)
         klaunch(cgl_head_loss_pk, dim3(L.grid + c->carry[L.pk].blocks), dim3(256), 0, s, c->head[L.first], L.grid,
                 c->carry[L.pk]);
       else
@@ -1586,7 +1790,10 @@ int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s) {
       klaunch(cgl_bn_bwd8, dim3(L.grid), dim3(256), 0, s, c->bnb[L.first]);
       break;
     case K_ADAM:
-      if (L.adpk)
+      if (L.adpk && L.nw > 1)
+        klaunch(cgl_adam_pack_grp, dim3(L.grid), dim3(256), 0, s, L.adam, c->adam_pack_d, c->ws.st, L.grid_y,
+                (long)c->nd, c->dpk_off);
+      else if (L.adpk)
         klaunch(cgl_adam_pack, dim3(L.grid), dim3(256), 0, s, L.adam, L.apk_d ? c->adam_pack_d : c->adam_pack,
                 c->ws.st, L.tail);
       else if (L.v4)
@@ -1617,6 +1824,12 @@ int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s) {
                                                                        c->ws.st, L.tail);
       break;
     case K_PROLOGUE:
+      if (c->nw > 1) {
+        klaunch(cgl_round_prologue_co, dim3(L.grid), dim3(256), 0, s, L.begin, L.nptr, L.nn, c->cfg.seed, L.nb_norm,
+                std::max(L.nb_samp, 1), c->ws.idx, c->cfg.epoch, c->cfg.batch_real, c->cfg.seed ^ 0x5bd1e995ULL,
+                c->shard, c->pack);
+        break;
+      }
       klaunch(cgl_round_prologue, dim3(L.grid), dim3(256), 0, s, L.begin, L.nptr, L.nn, c->cfg.seed,
                          L.nb_norm, c->ws.idx, c->cfg.epoch, c->cfg.batch_real, c->cfg.sample_n,
                          c->cfg.seed ^ 0x5bd1e995ULL, c->pack);
@@ -1693,12 +1906,18 @@ int64_t cgl_gan_workspace_bytes(const cgl_gan_config* cfg) {
   return carve_ws(*cfg, nullptr).total;
 }
 
-int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_gan** out) {
+static int gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, const int64_t* shard_row0,
+                      const int* shard_rows, cgl_gan** out) {
   CGL_BATCH_GUARD();
   if (!out || !bufs) return CGL_E_ARG;
   *out = nullptr;
   const int v = validate(cfg);
   if (v) return v;
+  if (shard_rows) {
+    if (cfg->colocated < 2 || cfg->sample_n <= 0 || !shard_row0) return CGL_E_ARG;
+    for (int q = 0; q < cfg->colocated; ++q)
+      if (shard_rows[q] < 1 || shard_row0[q] < 0) return CGL_E_ARG;
+  }
   if (!bufs->g_params || !bufs->g_grads || !bufs->g_m || !bufs->g_v || !bufs->d_params || !bufs->d_grads ||
       !bufs->d_m || !bufs->d_v || !bufs->z || !bufs->real || !bufs->workspace)
     return CGL_E_ARG;
@@ -1720,7 +1939,14 @@ int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_g
   c->bufs = *bufs;
   c->ws = carve_ws(*cfg, bufs->workspace);
   c->gl = param_layout(cfg->g, nullptr);
-  c->dl = param_layout(cfg->d, nullptr);
+  c->dl = param_layout(cfg->d, &c->nd);
+  c->nw = co_workers(*cfg);
+  c->shard.nw = c->nw;
+  for (int q = 0; q < c->nw; ++q) {      // the sampler's shards: the caller's table, or sample_n rows each
+    c->shard.rows[q] = shard_rows ? shard_rows[q] : cfg->sample_n;
+    c->shard_row0[q] = shard_rows ? shard_row0[q] : (int64_t)q * cfg->sample_n;
+    c->shard.idx_off[q] = c->ws.wk[q].idx - c->ws.wk[0].idx;
+  }
   running_layout(cfg->g, c->run_mean_off, c->run_var_off);
   int e = build_plan(c);
   if (e) {
@@ -1729,7 +1955,9 @@ int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_g
   }
   // the gathered exchange (cgl_gan_exchange_mode 1): the G-loss head also writes the loss into the word after the
   // exchange gradient, and phase B can start with cgl_alpha_combine over the gathered slots
-  if (c->xchg && c->ghead >= 0 && c->xchg_n % 4 == 0 && xchg_slot(c->xchg_n) <= xchg_slot_max(c->cfg)) {
+  // (co-located: the combine is part of the plan, the slots are written in place -- nothing to gather)
+  if (c->nw == 1 && c->xchg && c->ghead >= 0 && c->xchg_n % 4 == 0 &&
+      xchg_slot(c->xchg_n) <= xchg_slot_max(c->cfg)) {
     c->head[c->ghead].loss_out2 = c->xchg + c->xchg_n;
     Launch L;
     L.kind = K_COMBINE;
@@ -1760,9 +1988,9 @@ int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_g
     he = hipMemcpy(c->ws.bna, c->bna.data(), c->bna.size() * sizeof(CglBnApplyDesc), hipMemcpyHostToDevice);
   if (he == hipSuccess && !c->bnb.empty())
     he = hipMemcpy(c->ws.bnb, c->bnb.data(), c->bnb.size() * sizeof(CglBnBwdDesc), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemset(c->ws.counters, 0, kCounters * sizeof(unsigned int));
-  if (he == hipSuccess) he = hipMemset(c->ws.st, 0, sizeof(CglStepState));
-  if (he == hipSuccess) he = hipMemset(c->ws.rlog, 0, CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec));
+  if (he == hipSuccess) he = hipMemset(c->ws.counters, 0, counter_cap(*cfg) * sizeof(unsigned int));
+  if (he == hipSuccess) he = hipMemset(c->ws.st, 0, c->nw * sizeof(CglStepState));
+  if (he == hipSuccess) he = hipMemset(c->ws.rlog, 0, (size_t)c->nw * CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec));
   if (he == hipSuccess && c->z_ahead) {   // round 1's z
     const long nz = (long)2 * cfg->batch * cfg->g.dims[0];
     hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)((nz / 4 + 255) / 256)), dim3(256), 0, nullptr, c->ws.znext, nz,
@@ -1777,6 +2005,31 @@ int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_g
   }
   *out = c;
   return CGL_OK;
+}
+
+int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_gan** out) {
+  return gan_create(cfg, bufs, nullptr, nullptr, out);
+}
+
+int cgl_gan_create_sharded(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, const int64_t* shard_row0,
+                           const int* shard_rows, cgl_gan** out) {
+  if (!shard_row0 || !shard_rows) return CGL_E_ARG;
+  return gan_create(cfg, bufs, shard_row0, shard_rows, out);
+}
+
+// The packed weight copies from the current parameters (reset / cgl_gan_sync_params: G's and D's jobs; with_g false:
+// D's alone, cgl_gan_sync_params_d).  Co-located: pack_all / pack_d hold worker 0's D jobs, repeated per worker by
+// cgl_pack_all_grp.
+static void launch_pack_sync(cgl_gan* c, hipStream_t s, bool with_g) {
+  if (c->nw == 1) {
+    const CglOpPack& pk = with_g ? c->pack_all : c->pack_d;
+    if (pk.blocks > 0) hipLaunchKernelGGL(cgl_pack_all, dim3(pk.blocks), dim3(256), 0, s, pk);
+    return;
+  }
+  if (with_g && c->pack_g.blocks > 0) hipLaunchKernelGGL(cgl_pack_all, dim3(c->pack_g.blocks), dim3(256), 0, s, c->pack_g);
+  if (c->pack_d.blocks > 0)
+    hipLaunchKernelGGL(cgl_pack_all_grp, dim3(c->pack_d.blocks * c->nw), dim3(256), 0, s, c->pack_d, c->pack_d.blocks,
+                       (long)c->nd, c->dpk_off);
 }
 
 int cgl_gan_destroy(cgl_gan* c) {
@@ -1797,11 +2050,12 @@ int cgl_gan_reset(cgl_gan* c, const float* beta_host, void* stream) {
   h.scale[0] = h.scale[1] = c->cfg.loss_scale > 0.f ? c->cfg.loss_scale : 1.f;
   for (int i = 0; i < c->cfg.n_workers; ++i) h.beta[i] = beta_host ? beta_host[i] : 1.f / c->cfg.n_workers;
   hipStream_t s = (hipStream_t)stream;
-  HIPCHK(hipMemcpyAsync(c->ws.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(c->ws.counters, 0, kCounters * sizeof(unsigned int), s));
-  HIPCHK(hipMemsetAsync(c->ws.rlog, 0, CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec), s));   // a new timeline
+  for (int q = 0; q < c->nw; ++q)     // (co-located: every worker's block starts from the same reset state)
+    HIPCHK(hipMemcpyAsync(c->ws.st + q, &h, sizeof(h), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(c->ws.counters, 0, counter_cap(c->cfg) * sizeof(unsigned int), s));
+  HIPCHK(hipMemsetAsync(c->ws.rlog, 0, (size_t)c->nw * CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec), s));   // a new timeline
   if ((c->pack_adam || c->d_pack) && c->pack_all.blocks > 0) {   // the packed weights from the current parameters
-    hipLaunchKernelGGL(cgl_pack_all, dim3(c->pack_all.blocks), dim3(256), 0, s, c->pack_all);
+    launch_pack_sync(c, s, true);
     HIPCHK(hipGetLastError());
   }
   if (c->z_ahead) {                                   // the next round's z from the (reset) round counter
@@ -1828,7 +2082,7 @@ int cgl_gan_sync_params(cgl_gan* c, void* stream) {
   CGL_BATCH_GUARD();
   if (!c) return CGL_E_ARG;
   if ((c->pack_adam || c->d_pack) && c->pack_all.blocks > 0)   // (the prologue / carriers re-pack G every round)
-    hipLaunchKernelGGL(cgl_pack_all, dim3(c->pack_all.blocks), dim3(256), 0, (hipStream_t)stream, c->pack_all);
+    launch_pack_sync(c, (hipStream_t)stream, true);
   if (c->z_ahead) {
     const long nz = (long)2 * c->cfg.batch * c->cfg.g.dims[0];
     hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)((nz / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -1840,8 +2094,7 @@ int cgl_gan_sync_params(cgl_gan* c, void* stream) {
 int cgl_gan_sync_params_d(cgl_gan* c, void* stream) {
   CGL_BATCH_GUARD();
   if (!c) return CGL_E_ARG;
-  if (c->d_pack && c->pack_d.blocks > 0)
-    hipLaunchKernelGGL(cgl_pack_all, dim3(c->pack_d.blocks), dim3(256), 0, (hipStream_t)stream, c->pack_d);
+  if (c->d_pack && c->pack_d.blocks > 0) launch_pack_sync(c, (hipStream_t)stream, false);
   return (int)hipGetLastError();
 }
 
@@ -2026,10 +2279,10 @@ int cgl_gan_tensor(cgl_gan* c, int which, float** ptr, int64_t* n) {
     *n = c->cfg.epoch;
   } else if (which == 6) {                          // the device round state (CglStepState, raw words)
     *ptr = (float*)c->ws.st;
-    *n = (int64_t)(sizeof(CglStepState) / 4);
+    *n = (int64_t)(c->nw * sizeof(CglStepState) / 4);
   } else if (which == 7) {                          // the round log (cgl_gan_round_rec ring, raw words)
     *ptr = (float*)c->ws.rlog;
-    *n = (int64_t)(CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec) / 4);
+    *n = (int64_t)((size_t)c->nw * CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec) / 4);
   } else if (which == 5) {                          // the uploaded GEMM descriptor table (raw words)
     *ptr = (float*)c->ws.gemm;
     *n = (int64_t)(c->gemm.size() * sizeof(CglGemmDesc) / 4);
@@ -2067,21 +2320,27 @@ int cgl_gan_tensor(cgl_gan* c, int which, float** ptr, int64_t* n) {
 }
 
 int cgl_gan_read_stats(cgl_gan* c, cgl_gan_stats* out, void* stream) {
+  return cgl_gan_read_stats_worker(c, 0, out, stream);
+}
+
+int cgl_gan_read_stats_worker(cgl_gan* c, int worker, cgl_gan_stats* out, void* stream) {
   CGL_BATCH_GUARD();
-  if (!c || !out) return CGL_E_ARG;
-  CglStepState h;
+  if (!c || !out || worker < 0 || worker >= c->nw) return CGL_E_ARG;
+  CglStepState h, hw;
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipMemcpyAsync(&h, c->ws.st, sizeof(h), hipMemcpyDeviceToHost, s));
+  if (worker > 0) HIPCHK(hipMemcpyAsync(&hw, c->ws.st + worker, sizeof(hw), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  const CglStepState& k = worker > 0 ? hw : h;     // the worker's own losses; the rest is the server's
   std::memset(out, 0, sizeof(*out));
   out->round = h.round;
   for (int e = 0; e < CGL_MAX_EPOCH; ++e) {
-    out->d_loss[e] = h.d_loss[e];
-    out->d_real[e] = h.d_loss_parts[e][0];
-    out->d_fake[e] = h.d_loss_parts[e][1];
+    out->d_loss[e] = k.d_loss[e];
+    out->d_real[e] = k.d_loss_parts[e][0];
+    out->d_fake[e] = k.d_loss_parts[e][1];
   }
-  out->g_loss = h.g_loss_parts[0];
-  out->alpha = h.alpha;
+  out->g_loss = k.g_loss_parts[0];
+  out->alpha = worker > 0 ? h.alphas[worker] : h.alpha;
   out->F = h.F;
   out->lambda_ = h.lambda;
   out->bn_batches = h.bn_batches;
@@ -2098,15 +2357,22 @@ int cgl_gan_read_stats(cgl_gan* c, cgl_gan_stats* out, void* stream) {
 int cgl_gan_round_log_capacity(void) { return CGL_ROUND_LOG_CAP; }
 
 int cgl_gan_read_round_log(cgl_gan* c, int first_round, int count, cgl_gan_round_rec* out, void* stream) {
+  return cgl_gan_read_round_log_worker(c, 0, first_round, count, out, stream);
+}
+
+int cgl_gan_read_round_log_worker(cgl_gan* c, int worker, int first_round, int count, cgl_gan_round_rec* out,
+                                  void* stream) {
   CGL_BATCH_GUARD();
   if (!c || !out || first_round < 1 || count < 1 || count > CGL_ROUND_LOG_CAP) return CGL_E_ARG;
+  if (worker < 0 || worker >= c->nw) return CGL_E_ARG;
+  const cgl_gan_round_rec* ring = c->ws.rlog + (size_t)worker * CGL_ROUND_LOG_CAP;
   hipStream_t s = (hipStream_t)stream;
   // round r lives in slot (r - 1) % cap: one copy, or two when the range runs past the end of the ring
   const int slot0 = (int)(((int64_t)first_round - 1) % CGL_ROUND_LOG_CAP);
   const int n1 = std::min(count, CGL_ROUND_LOG_CAP - slot0);
-  HIPCHK(hipMemcpyAsync(out, c->ws.rlog + slot0, (size_t)n1 * sizeof(cgl_gan_round_rec), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(out, ring + slot0, (size_t)n1 * sizeof(cgl_gan_round_rec), hipMemcpyDeviceToHost, s));
   if (n1 < count)
-    HIPCHK(hipMemcpyAsync(out + n1, c->ws.rlog, (size_t)(count - n1) * sizeof(cgl_gan_round_rec),
+    HIPCHK(hipMemcpyAsync(out + n1, ring, (size_t)(count - n1) * sizeof(cgl_gan_round_rec),
                           hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   for (int i = 0; i < count; ++i)

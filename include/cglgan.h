@@ -88,7 +88,22 @@ typedef struct cgl_gan_config {
    * reference is fp32 only): parity unpinned. */
   float loss_scale;            /* initial S (torch's default init_scale: 65536), 0 = off             */
   int scale_growth_interval;   /* clean steps before S doubles (0: torch's default 2000)             */
+  /* Co-located workers (0 or 1: off).  W = 2 .. CGL_MAX_COLOCATED: this ONE context runs the whole W-worker
+   * round of a server group (capgan.py:211-262 + :316-349 with num_workers = W on one device, capgan.py:34-58):
+   * one generator replica, computed once, and the W workers' discriminators, every D stage of the round one
+   * launch over the W workers.  Then n_workers == W, rank == 0, exchange_layer == -1, loss_scale == 0 (CGL_E_ARG
+   * otherwise) and batch * g.dims[n_layers] % 4 == 0.  d_params / d_grads / d_m / d_v hold W models back to back
+   * (stride cgl_gan_param_count(cfg, CGL_MODEL_D)).  Without the sampler `real` is [W][epoch * batch_real][img]
+   * (worker-major); real_idx, when given, is [W][epoch * batch_real] indices into the whole of `real`.  With the
+   * sampler (sample_n > 0) cgl_gan_create takes W shards of sample_n rows each, back to back in `real`;
+   * cgl_gan_create_sharded takes shards of any lengths.  The exchange is local: worker q's G-loss gradient and
+   * loss land in slot q of the gathered buffer and cgl_alpha_combine forms sum_q alpha_q g_q in rank order, as
+   * exchange mode 1 does between ranks (cgl_gan_exchange_mode itself returns CGL_E_STATE: there is nothing to
+   * gather).  Each worker keeps its own round log and round scalars (cgl_gan_read_round_log_worker,
+   * cgl_gan_read_stats_worker); the calls without a worker argument report worker 0. */
+  int colocated;
 } cgl_gan_config;
+#define CGL_MAX_COLOCATED 16
 
 typedef struct cgl_gan_buffers {
   float* g_params; float* g_grads; float* g_m; float* g_v;  /* flat, cgl_gan_param_count(G)      */
@@ -155,6 +170,13 @@ int64_t cgl_gan_workspace_bytes(const cgl_gan_config* cfg);
  * workspace (capgan.py:211-262 + :316-349, mixed-gan.py:238-292 + :355-392,
  * MDGAN/MNIST/mdgan.py:180-207 + :266-297, CGLGAN/2DMG/main.py:225-278 + :344-375). */
 int cgl_gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, cgl_gan** out);
+/* cgl_gan_create for a co-located context (cfg->colocated = W >= 2) with the device sampler over shards of
+ * different lengths: worker w samples rows [shard_row0[w], shard_row0[w] + shard_rows[w]) of `real` (host arrays of
+ * W entries; every shard_rows[w] >= 1, cfg->sample_n > 0 switches the sampler on and is otherwise unused) --
+ * DataLoader(shuffle=True) over its own shard, the index stream a one-worker context with sample_n = shard_rows[w]
+ * and the same seed draws.  CGL_E_ARG when cfg is not co-located or the sampler is off. */
+int cgl_gan_create_sharded(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, const int64_t* shard_row0,
+                           const int* shard_rows, cgl_gan** out);
 int cgl_gan_destroy(cgl_gan* ctx);
 /* Zero the round counters / lambda, set the data-size weights beta[n_workers]
  * (capgan.py:149-153) -- host array.  Also refreshes the packed G weight copies (cgl_gan_sync_params). */
@@ -213,9 +235,11 @@ int cgl_gan_exchange_buffer(cgl_gan* ctx, float** ptr, int64_t* n);
  * 3 / 4 = device sampler (sample_n > 0): the round's real-row indices [epoch][batch_real] / real rows
  * of each local D step [epoch] (int32; a pass ends with a short batch of sample_n mod batch_real rows),
  * 5 = the round's GEMM descriptor table as uploaded by cgl_gan_create (raw 32-bit words),
- * 6 = the device round state (raw 32-bit words; what a resumed run saves and restores),
+ * 6 = the device round state (raw 32-bit words; what a resumed run saves and restores; co-located: the W
+ *     workers' blocks back to back),
  * 7 = the round log, CGL_ROUND_LOG_CAP records of cgl_gan_round_rec as raw 32-bit words (a caller that writes
- *     the round state from outside -- a resumed run -- zeroes it: the records belong to the old timeline),
+ *     the round state from outside -- a resumed run -- zeroes it: the records belong to the old timeline;
+ *     co-located: the W workers' rings back to back),
  * 16+l / 32+l = gradient w.r.t. layer l's activation / Linear output [B][dims[l+1]] (Xg rows),
  * 48+l / 64+l = layer l's BN+LeakyReLU output / Linear output [2B][dims[l+1]],
  * 80+l / 96+l = saved BN batch mean / invstd [2][dims[l+1]],
@@ -224,6 +248,10 @@ int cgl_gan_exchange_buffer(cgl_gan* ctx, float** ptr, int64_t* n);
 int cgl_gan_tensor(cgl_gan* ctx, int which, float** ptr, int64_t* n);
 /* Synchronous copy of the round scalars to the host. */
 int cgl_gan_read_stats(cgl_gan* ctx, cgl_gan_stats* out, void* stream);
+/* The same for worker `worker` of a co-located context (its D losses, G loss and alpha; round, F, lambda_ and
+ * bn_batches belong to the shared server).  worker 0 of any context = cgl_gan_read_stats.  CGL_E_ARG for a worker
+ * the context does not have. */
+int cgl_gan_read_stats_worker(cgl_gan* ctx, int worker, cgl_gan_stats* out, void* stream);
 /* Round log: capacity of the ring in records (host only; CGL_ROUND_LOG_CAP, >= 4 * CGL_MAX_GRAPH_ROUNDS). */
 int cgl_gan_round_log_capacity(void);
 /* Copy the records of rounds first_round ... first_round + count - 1 to the host array `out` (count records): at
@@ -235,6 +263,11 @@ int cgl_gan_round_log_capacity(void);
  * copied record does not hold the round asked for (not run yet, overwritten by round + CGL_ROUND_LOG_CAP, or
  * cleared); `out` is then unspecified. */
 int cgl_gan_read_round_log(cgl_gan* ctx, int first_round, int count, cgl_gan_round_rec* out, void* stream);
+/* The same from worker `worker`'s ring (a co-located context keeps one ring per worker, all written by the
+ * round's tail launch; worker 0 of any context = cgl_gan_read_round_log).  CGL_E_ARG for a worker the context does
+ * not have. */
+int cgl_gan_read_round_log_worker(cgl_gan* ctx, int worker, int first_round, int count, cgl_gan_round_rec* out,
+                                  void* stream);
 /* Launch / kernel counts of a phase (for roofline bookkeeping). */
 int cgl_gan_plan_info(cgl_gan* ctx, int phase, int* n_launches, int* n_gemm_launches, double* gemm_flops);
 /* Per-launch access to the plan (instrumented timing: the caller brackets each launch with

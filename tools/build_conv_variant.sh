@@ -9,7 +9,7 @@ mkdir -p build lib_$tag
 /opt/rocm/bin/hipcc $FLAGS $defs -c csrc/cgl_conv_tu.hip -o build/cvar_$tag.o &
 /opt/rocm/bin/hipcc $FLAGS $defs -c csrc/cgl_conv_bf16.hip -o build/cvar_${tag}_bf16.o &   # (the bf16 kernel instances)
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared build/cgl_runtime.o build/cgl_gemm_p1.o build/cgl_gemm_p2.o build/cgl_gemm_p3.o build/cvar_$tag.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared build/cgl_runtime.o build/cgl_gemm_p1.o build/cgl_gemm_p2.o build/cgl_gemm_p3.o build/cgl_gemm_p4.o build/cgl_gemm_p5.o build/cvar_$tag.o \
   build/cvar_${tag}_bf16.o \
   -o lib_$tag/libcglgan_hip.so
 echo "built lib_$tag ($defs)"
