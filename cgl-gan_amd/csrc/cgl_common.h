@@ -148,6 +148,10 @@ __device__ __forceinline__ void cgl_normal_at(long q, float* out, long n, unsign
     if (q * 4 + j < n) out[q * 4 + j] = z[j];
 }
 
+// 256-thread blocks of a launch that draws n outputs with cgl_normal_at: one thread per four outputs, ceil(n / 4)
+// threads -- n / 4 would leave the last n % 4 outputs of n = 1024 k + 1 .. 3 undrawn (and launch nothing for n < 4)
+inline long cgl_normal_blocks(long n) { return ((n + 3) / 4 + 255) / 256; }
+
 // Shuffle sampler: keyed Feistel permutation of [0, n) per data epoch (cycle walking).
 __device__ __forceinline__ uint32_t cgl_hash(uint32_t x, uint32_t k) {
   x ^= k;

@@ -5296,10 +5296,10 @@ int cgl_normal_fill_dev(float* out, int64_t n, unsigned long long seed, const in
     if (t_batch.a.nb || (hipStream_t)stream != t_batch.s) return CGL_E_ARG;
     CglConvBeginArgs& b = t_batch.a;
     b.n_out = out; b.n_n = (long)n; b.n_seed = seed; b.n_round = round_dev; b.n_sid = stream_id;
-    b.nb = (int)((n / 4 + 255) / 256);
+    b.nb = (int)cgl_normal_blocks(n);
     return 0;
   }
-  hipLaunchKernelGGL(cgl_normal_dev_k, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out,
+  hipLaunchKernelGGL(cgl_normal_dev_k, dim3((unsigned)cgl_normal_blocks(n)), dim3(256), 0, (hipStream_t)stream, out,
                      (long)n, seed, round_dev, stream_id);
   return (int)hipGetLastError();
 }

@@ -1051,7 +1051,7 @@ bool build_adam_pack(const CglOpPackJob* jobs, int nj, const std::vector<TensorR
   A.adpk = true;
   if (A.adam.znext) {           // the z-ahead blocks come after the parameter blocks
     A.adam.zblk0 = blk;
-    blk += (int)((A.adam.nz / 4 + 255) / 256);
+    blk += (int)cgl_normal_blocks(A.adam.nz);
   }
   A.grid = blk;
   out = pk;
@@ -1201,7 +1201,7 @@ int build_plan(cgl_gan* c) {
     if (cf.gen_z && !c->z_ahead) {
       Lp.nptr = c->bufs.z;
       Lp.nn = (long)2 * B * g.dims[0];
-      Lp.nb_norm = (int)((Lp.nn / 4 + 255) / 256);
+      Lp.nb_norm = (int)cgl_normal_blocks(Lp.nn);
     }
     if (cf.sample_n > 0) {
       Lp.nb_samp = (cf.epoch * Br + 255) / 256;       // (co-located: per worker)
@@ -1691,7 +1691,7 @@ int build_plan(cgl_gan* c) {
     Ag.adam.nz = (long)2 * B * g.dims[0];
     Ag.adam.zseed = cf.seed;
     Ag.adam.zblk0 = Ag.grid;
-    Ag.grid += (int)((Ag.adam.nz / 4 + 255) / 256);
+    Ag.grid += (int)cgl_normal_blocks(Ag.adam.nz);
   }
   fuse_wgrad_adam(c, *ph, CGL_MODEL_G);
   defer_heads(c);      // (before the packing plan: the deferred heads can carry packing jobs)
@@ -1993,7 +1993,7 @@ static int gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, co
   if (he == hipSuccess) he = hipMemset(c->ws.rlog, 0, (size_t)c->nw * CGL_ROUND_LOG_CAP * sizeof(cgl_gan_round_rec));
   if (he == hipSuccess && c->z_ahead) {   // round 1's z
     const long nz = (long)2 * cfg->batch * cfg->g.dims[0];
-    hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)((nz / 4 + 255) / 256)), dim3(256), 0, nullptr, c->ws.znext, nz,
+    hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)cgl_normal_blocks(nz)), dim3(256), 0, nullptr, c->ws.znext, nz,
                        cfg->seed, (const CglStepState*)c->ws.st);
     he = hipGetLastError();
     if (he == hipSuccess) he = hipDeviceSynchronize();
@@ -2060,7 +2060,7 @@ int cgl_gan_reset(cgl_gan* c, const float* beta_host, void* stream) {
   }
   if (c->z_ahead) {                                   // the next round's z from the (reset) round counter
     const long nz = (long)2 * c->cfg.batch * c->cfg.g.dims[0];
-    hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)((nz / 4 + 255) / 256)), dim3(256), 0, s, c->ws.znext, nz,
+    hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)cgl_normal_blocks(nz)), dim3(256), 0, s, c->ws.znext, nz,
                        c->cfg.seed, (const CglStepState*)c->ws.st);
     HIPCHK(hipGetLastError());
   }
@@ -2085,7 +2085,7 @@ int cgl_gan_sync_params(cgl_gan* c, void* stream) {
     launch_pack_sync(c, (hipStream_t)stream, true);
   if (c->z_ahead) {
     const long nz = (long)2 * c->cfg.batch * c->cfg.g.dims[0];
-    hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)((nz / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(cgl_znext_draw, dim3((unsigned)cgl_normal_blocks(nz)), dim3(256), 0, (hipStream_t)stream,
                        c->ws.znext, nz, c->cfg.seed, (const CglStepState*)c->ws.st);
   }
   return (int)hipGetLastError();
@@ -2702,7 +2702,7 @@ int cgl_normal_fill(float* out, int64_t n, unsigned long long seed, int round, i
   CGL_BATCH_GUARD();
   if (!out || n < 0) return CGL_E_ARG;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(cgl_normal, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out,
+  hipLaunchKernelGGL(cgl_normal, dim3((unsigned)cgl_normal_blocks(n)), dim3(256), 0, (hipStream_t)stream, out,
                      (long)n, seed, round, stream_id);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;

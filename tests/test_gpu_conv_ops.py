@@ -399,3 +399,126 @@ def test_dense1_head_nhwc_bitwise(n):
     xr = nchw(x.cpu().double()).reshape(n, 512)
     close(y_new, xr @ w.cpu().double().t() + b.cpu().double(), what="head fwd")
     close(dx_new, nhwc((dy.cpu().double() @ w.cpu().double()).reshape(n, 128, 2, 2)), what="head bwd")
+
+
+# ---------------------------------------------------------------------------------------------------
+# cgl_weights_scale (the five alpha weightings of the exchange, cgl_weights in csrc/cgl_common.h) and
+# cgl_counters_add, against fp64 restatements of the reference formulas.
+def _alpha64(weighting, lam, losses, beta):
+    """fp64 alpha of the reference's Server.train, from the fp32 inputs the kernel gets"""
+    from oracle.gan_oracle import capgan_alpha
+    l, b = losses.double(), beta.double()
+    n = l.numel()
+    if weighting == "capgan":          # capgan.py:247-248: softmax(softmax(lam l) beta)
+        return capgan_alpha(lam, l, b)
+    if weighting == "mean":            # MDGAN/MNIST/mdgan.py:203: the plain average
+        return torch.full((n,), 1.0 / n, dtype=torch.float64)
+    if weighting == "mix_single":      # mixed-gan.py:276: softmax(beta lam l)
+        return F.softmax(b * lam * l, dim=0)
+    gamma = F.softmax(lam * l, dim=0)
+    if weighting == "mix_double":      # CAPGAN/MNIST/mixed-gan.py:276-277: softmax(beta softmax(lam l))
+        return F.softmax(b * gamma, dim=0)
+    assert weighting == "cglgan"       # CGLGAN/2DMG/main.py:261-264: (beta + softmax(lam l)) / 2
+    return (b + gamma) / 2
+
+
+WEIGHTINGS = ["capgan", "mean", "mix_single", "mix_double", "cglgan"]
+
+
+@pytest.mark.parametrize("n", [1, 2, 10, 64])
+@pytest.mark.parametrize("weighting", WEIGHTINGS)
+def test_weights_scale_alpha(weighting, n):
+    """alpha_out within 1e-5 relative per element of the fp64 formula (softmax arguments up to |15|: their fp32
+    rounding, 15 * 2^-24 ~ 9e-7, and expf's 2 ulp give ~2e-6 per softmax; two nested; a margin), the four
+    softmax-normalised weightings sum to 1 within N 2^-22, `mean` is exactly fp32(1 / N), and the scaled buffer is
+    bitwise x * alpha_out[rank] (one fp32 multiply).  Worst relative alpha error measured on the MI355X: 4.0e-7
+    (cglgan, N = 64)."""
+    import numpy as np
+    g = torch.Generator().manual_seed(100 * n + len(weighting))
+    worst = 0.0
+    ranks = range(n) if n <= 10 else (0, 17, n - 1)
+    for lam in (0.1, 1.0, 5.0):
+        lam32 = float(np.float32(lam))
+        losses = (0.3 + 2.7 * torch.rand(n, generator=g)).float()
+        beta = torch.rand(n, generator=g).double() + 0.05
+        beta = (beta / beta.sum()).float()
+        ref = _alpha64(weighting, lam32, losses, beta)
+        x0 = torch.randn(300, generator=g)
+        for rank in ranks:
+            x = x0.cuda()
+            alpha = torch.full((n + 4,), -7.0, device=DEV)
+            ops().weights_scale(weighting, lam, beta.tolist(), losses.cuda(), rank, x=x, alpha_out=alpha[:n])
+            torch.cuda.synchronize()
+            assert (alpha[n:] == -7.0).all(), "stores past alpha_out[n]"
+            a = alpha[:n].cpu()
+            rel = float(((a.double() - ref).abs() / ref).max())
+            worst = max(worst, rel)
+            assert rel <= 1e-5, f"{weighting} n={n} lam={lam} rank={rank}: alpha off by {rel:.3e} relative"
+            if weighting == "mean":
+                assert torch.equal(a, torch.full((n,), 1.0, dtype=torch.float32) / torch.tensor(float(n)))
+            else:
+                assert abs(float(a.double().sum()) - 1.0) <= n * 2.0 ** -22
+            assert torch.equal(x.cpu(), x0 * a[rank]), f"{weighting} n={n} rank={rank}: x is not x * alpha[rank]"
+    print(f"weights_scale {weighting} n={n}: worst relative alpha error {worst:.3e} (bound 1e-5)")
+
+
+@pytest.mark.parametrize("nx", [0, 1, 255, 257, 1024 * 256 + 3])
+def test_weights_scale_buffer(nx):
+    """x[0:nx] *= alpha[rank] for every nx (the last wraps the 1024-block grid-stride loop), nothing past nx is
+    touched, and alpha_out = None leaves the same x."""
+    n, rank, lam = 3, 1, 1.5
+    g = torch.Generator().manual_seed(nx + 1)
+    losses = (0.3 + 2.7 * torch.rand(n, generator=g)).float().cuda()
+    beta = [0.2, 0.5, 0.3]
+    x0 = torch.randn(nx + 8, generator=g)
+    alpha = torch.zeros(n, device=DEV)
+    xa = x0.cuda()
+    ops().weights_scale("capgan", lam, beta, losses, rank, x=xa[:nx], alpha_out=alpha)
+    xb = x0.cuda()
+    ops().weights_scale("capgan", lam, beta, losses, rank, x=xb[:nx], alpha_out=None)
+    torch.cuda.synchronize()
+    want = x0.clone()
+    want[:nx] = x0[:nx] * alpha.cpu()[rank]
+    assert torch.equal(xa.cpu(), want)
+    assert torch.equal(xb.cpu(), want)
+    ref = _alpha64("capgan", float(torch.tensor(lam, dtype=torch.float32)), losses.cpu(), torch.tensor(beta))
+    close(alpha, ref, rel=1e-5, what="alpha")
+
+
+def test_weights_scale_and_counters_bad_arguments():
+    import ctypes
+    from cglgan import _lib as C
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    losses = torch.ones(80, device=DEV)
+    x0 = torch.randn(16)
+    x = x0.cuda()
+    beta = (ctypes.c_float * 80)(*([1.0 / 80] * 80))
+
+    def ws(weighting=0, n=4, rank=0, beta=beta, losses=p(losses), xp=p(x), nx=16):
+        return C.lib.cgl_weights_scale(weighting, n, rank, 1.0, beta, losses, xp, nx, None, s)
+
+    for bad in (dict(weighting=5), dict(weighting=-1), dict(n=65), dict(n=0), dict(rank=4), dict(rank=-1),
+                dict(beta=None), dict(losses=None), dict(xp=None), dict(nx=-1)):
+        assert ws(**bad) == -1, bad
+    assert ws(n=64, rank=63, nx=0, xp=None) == 0
+    cnt = torch.arange(80, dtype=torch.int32, device=DEV)
+    for bad in (dict(n=65), dict(n=0), dict(n=-1)):
+        assert C.lib.cgl_counters_add(p(cnt), bad["n"], 1, s) == -1, bad
+    assert C.lib.cgl_counters_add(None, 4, 1, s) == -1
+    torch.cuda.synchronize()
+    assert torch.equal(x.cpu(), x0) and torch.equal(cnt.cpu(), torch.arange(80, dtype=torch.int32))
+
+
+@pytest.mark.parametrize("v", [1, -2])
+@pytest.mark.parametrize("n", [1, 3, 64])
+def test_counters_add(n, v):
+    """p[i] += v for i < n; the words past n stay"""
+    c0 = torch.arange(5, 5 + n + 8, dtype=torch.int32)
+    buf = c0.cuda()
+    ops().counters_add(buf[:n], v)
+    ops().counters_add(buf[:n], v)
+    torch.cuda.synchronize()
+    want = c0.clone()
+    want[:n] += 2 * v
+    assert torch.equal(buf.cpu(), want)
