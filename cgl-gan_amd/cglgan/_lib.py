@@ -65,7 +65,7 @@ class GanConfig(ctypes.Structure):
                 ("bn_momentum", ctypes.c_double), ("slope", ctypes.c_float), ("seed", ctypes.c_ulonglong),
                 ("gen_z", ctypes.c_int), ("sample_n", ctypes.c_int), ("gemm_dtype", ctypes.c_int),
                 ("loss_scale", ctypes.c_float), ("scale_growth_interval", ctypes.c_int),
-                ("colocated", ctypes.c_int)]
+                ("colocated", ctypes.c_int), ("colocated_heads", ctypes.c_int)]
 
 
 class GanBuffers(ctypes.Structure):

@@ -15,7 +15,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib as C
-from .specs import MlpModel
+from .specs import MlpGroupModel, MlpModel
 
 _WEIGHTING = {"capgan": C.WEIGHT_CAPGAN, "mean": C.WEIGHT_MEAN, "mix_single": C.WEIGHT_MIX_SINGLE,
               "mix_double": C.WEIGHT_MIX_DOUBLE, "cglgan": C.WEIGHT_CGLGAN}
@@ -68,6 +68,16 @@ class GanStep:
     one-worker step over its shard draws with the same seed.  ``run``, ``run_rounds``, ``prepare_rounds``,
     ``resume_state`` / ``load_resume_state`` and ``sync_params`` work as on the one-worker step; the ``.data``-write
     caveat above and the version-counter refresh cover the whole ``[W, nd]`` block.
+
+    Co-located Mix-G / CGLGAN (``GanStep(specs.mixgen_group(W), d, colocated=W, exchange_layer=spec.head_layer,
+    weighting="mix_single" | "mix_double" | "cglgan")``): the step's generator is the server's whole
+    ``MixGenerator(ims, W)`` -- the trunk, run once, and one head per worker, every head stage one launch over the W
+    heads (cgl_gan_config.colocated_heads).  ``g_params`` / ``g_grads`` / ``g_m`` / ``g_v`` hold
+    ``[trunk | head 0 | ... | head W-1]``; ``g_views`` / ``g_grad_views`` / ``running`` / ``g_state_dict()`` carry the
+    module's own keys (``model.*``, ``paths.<h>.*``), so a state dict of the reference's ``MixGenerator`` loads as-is
+    and a saved one loads back into it.  ``exchange_buffer()`` is the combined hidden-layer gradient,
+    ``trunk_slices()`` the trunk for the Cloud average; ``internal(code + 256 * w)`` reads worker w's copy of an
+    internal tensor.
     """
 
     def __init__(self, g: MlpModel, d: MlpModel, batch: int, batch_real: int = None, epoch: int = 1,
@@ -91,8 +101,9 @@ class GanStep:
         if W:
             if W > C.MAX_COLOCATED:
                 raise ValueError(f"colocated: at most {C.MAX_COLOCATED} workers share a step")
-            if exchange_layer != -1:
-                raise ValueError("colocated: the G-output exchange only (Mix-G's per-worker heads are not planned)")
+            if exchange_layer != -1 and not isinstance(g, MlpGroupModel):
+                raise ValueError("colocated: the G-output exchange only (Mix-G's per-worker heads are planned from "
+                                 "the group's whole generator: specs.mixgen_group(W) / specs.ring_group(W))")
             if loss_scale:
                 raise ValueError("colocated: loss scaling is not supported")
             if n_workers not in (1, W) or rank != 0:
@@ -100,6 +111,10 @@ class GanStep:
             n_workers = W
         elif shards is not None:
             raise ValueError("shards: a co-located step's sampler table")
+        heads = isinstance(g, MlpGroupModel)
+        if heads and (not W or g.heads != W or exchange_layer != g.head_layer):
+            raise ValueError(f"{g.name}: a group generator runs co-located, one head per worker, split at its head "
+                             f"layer (colocated={g.heads}, exchange_layer={g.head_layer})")
         self.B = batch
         self.Br = batch_real or batch
         self.epoch = epoch
@@ -122,6 +137,7 @@ class GanStep:
             raise ValueError("loss_scale applies to the 16-bit GEMM paths (gemm_dtype f16 / bf16)")
         cfg.loss_scale, cfg.scale_growth_interval = float(loss_scale), int(scale_growth_interval)
         cfg.colocated = W
+        cfg.colocated_heads = int(heads)
         self.cfg = cfg
         self.n_workers, self.rank = n_workers, rank
         self.exchange_layer = exchange_layer
@@ -226,13 +242,19 @@ class GanStep:
         rend = sum(2 * al(self.gm.dims[l + 1]) for l in self.gm.bn_layers() if l < self.exchange_layer)
         return p, (self.g_running[:rend] if rend > 0 else None)
 
+    def _bn_modules(self):
+        """(state-dict prefix, layer) of G's BatchNorm modules in running-statistics buffer order (a group
+        generator: the trunk's, then head 0's, head 1's, ...)."""
+        if isinstance(self.gm, MlpGroupModel):
+            return [(p, l) for p, l, _ in self.gm.running_prefixes()]
+        return [(self.gm.bn_keys[l], l) for l in self.gm.bn_layers()]
+
     def _running_views(self):
         self.running = OrderedDict()
         off = 0
         al = lambda n: (n + 63) // 64 * 64
-        for l in self.gm.bn_layers():
+        for k, l in self._bn_modules():
             n = self.gm.dims[l + 1]
-            k = self.gm.bn_keys[l]
             self.running[k + ".running_mean"] = self.g_running[off:off + n]
             off += al(n)
             self.running[k + ".running_var"] = self.g_running[off:off + n]
@@ -272,8 +294,7 @@ class GanStep:
         st = self.stats()
         for k, v in self.g_views.items():
             sd[k] = v.detach().clone()
-        for l in self.gm.bn_layers():
-            k = self.gm.bn_keys[l]
+        for k, _ in self._bn_modules():
             sd[k + ".running_mean"] = self.running[k + ".running_mean"].clone()
             sd[k + ".running_var"] = self.running[k + ".running_var"].clone()
             sd[k + ".num_batches_tracked"] = torch.tensor(st["bn_batches"], dtype=torch.long)

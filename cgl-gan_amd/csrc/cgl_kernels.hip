@@ -355,8 +355,10 @@ __device__ __forceinline__ void cgl_bnb_store_gb(const CglBnBwdDesc* __restrict_
 }
 // FPW features per workgroup (32: the single-op form; 8, the round's, gives 4x the workgroups for the narrow
 // layers, each thread then owning fewer rows): NRG = 256 / FPW row groups, rows of a group in registers.
+// (bid of nblk: the workgroup's place in this descriptor's grid -- the launch's own, or a worker's share of a
+// grouped launch, cgl_bn_bwd8_grp)
 template <int FPW>
-__device__ __forceinline__ void cgl_bn_bwd_body(const CglBnBwdDesc* __restrict__ bd) {
+__device__ __forceinline__ void cgl_bn_bwd_body(const CglBnBwdDesc* __restrict__ bd, int bid, int nblk) {
   constexpr int NRG = 256 / FPW, RPT = 256 / NRG;   // register path: M <= NRG * RPT = 256
   __shared__ double s_a[NRG][FPW], s_b[NRG][FPW];
   const int M = bd->M, F = bd->F;
@@ -364,9 +366,9 @@ __device__ __forceinline__ void cgl_bn_bwd_body(const CglBnBwdDesc* __restrict__
   // XCD-contiguous feature slices: workgroup b runs on XCD b % 8, so give each XCD a contiguous range of
   // slices -- the 128 / (4 FPW) slices that share a row's 128-byte lines then fetch (and write) them through
   // one L2 instead of up to four (FPW = 8: 4x the dA / post / Y fetch, profiles/r04_traffic.json)
-  int blk = blockIdx.x;
-  if (gridDim.x >= 16) {
-    const int nb = gridDim.x, xcd = blk & 7, pos = blk >> 3, q = nb >> 3, rr = nb & 7;
+  int blk = bid;
+  if (nblk >= 16) {
+    const int nb = nblk, xcd = blk & 7, pos = blk >> 3, q = nb >> 3, rr = nb & 7;
     blk = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + pos;
   }
   const int f = blk * FPW + fl;
@@ -499,9 +501,26 @@ __global__ __launch_bounds__(256) void cgl_head_loss_grp(const CglHeadDesc* __re
 __global__ __launch_bounds__(256) void cgl_bn_apply(const CglBnApplyDesc d) {
   cgl_bn_apply_body(&d, blockIdx.x, blockIdx.y);
 }
-__global__ __launch_bounds__(256) void cgl_bn_bwd8(const CglBnBwdDesc d) { cgl_bn_bwd_body<8>(&d); }
+__global__ __launch_bounds__(256) void cgl_bn_bwd8(const CglBnBwdDesc d) {
+  cgl_bn_bwd_body<8>(&d, blockIdx.x, gridDim.x);
+}
 // the single-op entry point (cgl_bn1d_bwd): the descriptor travels in the kernel arguments
-__global__ __launch_bounds__(256) void cgl_bn_bwd_arg(const CglBnBwdDesc d) { cgl_bn_bwd_body<32>(&d); }
+__global__ __launch_bounds__(256) void cgl_bn_bwd_arg(const CglBnBwdDesc d) {
+  cgl_bn_bwd_body<32>(&d, blockIdx.x, gridDim.x);
+}
+// A head's BatchNorm of the W co-located Mix-G heads as one launch (cgl_gan_config.colocated_heads): workgroups
+// [w wgs, (w + 1) wgs) run head w's cgl_bn_apply grid (gx feature blocks x wgs / gx row blocks, row-major) /
+// cgl_bn_bwd8 grid (descriptor descs[w] in memory: same shape for every head, its own rows, statistics, gamma /
+// beta and outputs), each the one-head kernel's body -- so head w's activations, statistics and gradients are
+// bitwise those of its own launch.  No workgroup waits for another.
+__global__ __launch_bounds__(256) void cgl_bn_apply_grp(const CglBnApplyDesc* __restrict__ descs, int gx, int wgs) {
+  const int w = blockIdx.x / wgs, b = (int)blockIdx.x - w * wgs;
+  cgl_bn_apply_body(descs + w, b % gx, b / gx);
+}
+__global__ __launch_bounds__(256) void cgl_bn_bwd8_grp(const CglBnBwdDesc* __restrict__ descs, int wgs) {
+  const int w = blockIdx.x / wgs;
+  cgl_bn_bwd_body<8>(descs + w, (int)blockIdx.x - w * wgs, wgs);
+}
 #endif   // CGL_GEMM_PART_TU
 // ------------------------------------------------------------------------------------------
 // Standalone BatchNorm1d (+ LeakyReLU) forward, train or eval, for the nn.Module path.  One

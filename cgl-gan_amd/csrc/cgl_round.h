@@ -106,12 +106,28 @@ __global__ __launch_bounds__(256) void cgl_pack_all_grp(CglOpPack pk, int wblock
 // next nb_norm blocks the z draw, then nb_samp sampler blocks per worker -- worker w draws its own index list from
 // its own shard (sh.rows[w] rows; the stream of a one-worker context over that shard) and writes its batches' real
 // rows into st[w] -- and the packing blocks last.
+// Co-located Mix-G heads (hpk.blocks > 0): ahead of those, the packing jobs of head 0's weight matrices (hpk)
+// repeated for every head as in cgl_pack_all_grp -- head w's sources hstride floats after head 0's, its packed
+// copies at hoff.d[w].
 __global__ __launch_bounds__(256) void cgl_round_prologue_co(CglBeginArgs a, float* z, long nz, unsigned long long zseed,
                                                              int nb_norm, int nb_samp, int* idx, int epoch, int br,
-                                                             unsigned long long sseed, CglCoShard sh, CglOpPack pk) {
+                                                             unsigned long long sseed, CglCoShard sh, CglOpPack pk,
+                                                             CglOpPack hpk, long hstride, CglCoOff hoff) {
   const int bid = blockIdx.x, nblk = gridDim.x;
   const int done = a.st->round;
   const int pk0 = nblk - pk.blocks;
+  const int hp0 = pk0 - hpk.blocks * sh.nw;
+  if (bid >= hp0 && bid < pk0) {
+    const int w = (bid - hp0) / hpk.blocks, b = (bid - hp0) - w * hpk.blocks;
+    int j = 0;
+    for (int q = 1; q < hpk.nj; ++q)
+      if (b >= hpk.j[q].blk_begin) j = q;
+    CglOpPackJob J = hpk.j[j];
+    J.src += (long)w * hstride;
+    J.dst += hoff.d[w];
+    cgl_pack_job(J, (long)(b - J.blk_begin) * 256 + threadIdx.x);
+    return;
+  }
   if (bid >= pk0) {
     const int b = bid - pk0;
     int j = 0;

@@ -109,17 +109,59 @@ int validate(const cgl_gan_config* c) {
     if (!std::isfinite(c->loss_scale) || std::frexp(c->loss_scale, &ex) != 0.5f) return CGL_E_ARG;
     if (c->gemm_dtype == CGL_DTYPE_F32 || c->epoch != 1) return CGL_E_ARG;
   }
-  // co-located workers: the whole group in this context (rank 0 stands for it), the G-output exchange only (Mix-G's
-  // per-worker heads are not planned), no loss scaling (one found flag per model), a combinable exchange slot
-  if (c->colocated < 0) return CGL_E_ARG;
+  // co-located workers: the whole group in this context (rank 0 stands for it), the G-output exchange (Mix-G's
+  // per-worker heads: colocated_heads, below), no loss scaling (one found flag per model), a combinable exchange slot
+  // co-located Mix-G heads (colocated_heads): the context's G is the trunk and the W workers' heads, the exchange
+  // the gradient of the first head layer's input
+  if (c->colocated < 0 || (c->colocated_heads != 0 && c->colocated_heads != 1)) return CGL_E_ARG;
+  if (c->colocated_heads && c->colocated < 2) return CGL_E_ARG;
   if (c->colocated > 1) {
     if (c->colocated > CGL_MAX_COLOCATED || c->n_workers != c->colocated || c->rank != 0) return CGL_E_ARG;
-    if (c->exchange_layer != -1 || c->loss_scale > 0.f) return CGL_E_ARG;
-    if (((int64_t)c->batch * g.dims[g.n_layers]) % 4 != 0) return CGL_E_ARG;
+    if (c->loss_scale > 0.f) return CGL_E_ARG;
+    if (c->colocated_heads ? c->exchange_layer == -1 : c->exchange_layer != -1) return CGL_E_ARG;
+    const int xf = c->colocated_heads ? g.dims[c->exchange_layer] : g.dims[g.n_layers];
+    if (((int64_t)c->batch * xf) % 4 != 0) return CGL_E_ARG;
   }
   return CGL_OK;
 }
 inline int co_workers(const cgl_gan_config& c) { return c.colocated > 1 ? c.colocated : 1; }
+// co-located Mix-G heads: the first head layer (0: the context has one generator for all its workers)
+inline int co_head_layer(const cgl_gan_config& c) { return c.colocated > 1 && c.colocated_heads ? c.exchange_layer : 0; }
+
+// The G buffers of a context.  One generator: param_layout(cfg.g).  Co-located Mix-G heads: the trunk's tensors,
+// then W copies of the head's (cfg.g = trunk + one head; head q's tensors head_stride floats after head 0's), the
+// running statistics alike.
+struct GLayout {
+  std::vector<TensorRec> one;    // trunk + head 0 (the whole model without heads)
+  int n_trunk = 0;               // tensors of the trunk (all of them without heads)
+  int heads = 1;
+  int64_t trunk = 0, head_stride = 0, total = 0;            // floats
+  int64_t run_trunk = 0, run_stride = 0, run_total = 0;
+};
+GLayout g_layout(const cgl_gan_config& c) {
+  GLayout y;
+  int64_t n1 = 0;
+  y.one = param_layout(c.g, &n1);
+  const int xl = co_head_layer(c);
+  const int64_t r1 = running_layout(c.g, nullptr, nullptr);
+  y.n_trunk = (int)y.one.size();
+  y.trunk = y.total = n1;
+  y.run_trunk = y.run_total = r1;
+  if (xl > 0) {
+    y.heads = c.colocated;
+    y.n_trunk = 0;
+    while (y.n_trunk < (int)y.one.size() && y.one[y.n_trunk].layer < xl) ++y.n_trunk;
+    y.trunk = y.one[y.n_trunk].off;
+    y.head_stride = n1 - y.trunk;
+    y.total = y.trunk + y.heads * y.head_stride;
+    y.run_trunk = 0;
+    for (int l = 0; l < xl; ++l)
+      if (c.g.bn[l]) y.run_trunk += 2 * al64(c.g.dims[l + 1]);
+    y.run_stride = r1 - y.run_trunk;
+    y.run_total = y.run_trunk + y.heads * y.run_stride;
+  }
+  return y;
+}
 
 // ----------------------------------------------------------------------------------------
 // workspace carve (sizing pass with base == nullptr)
@@ -144,9 +186,15 @@ constexpr int kCounters = 64;                    // head-loss tickets
 // Descriptor table and ticket sizes of a context.  One worker: the constants above (the carve every context had).
 // Co-located: worker w's D adds, per local D step, J - 1 forwards, J weight gradients and J - 1 input gradients,
 // plus 2 (J - 1) GEMMs of the G-loss pass, one head per local step and one for the G loss, each head its own ticket.
+// Co-located Mix-G heads: each head layer adds, per worker, one forward, one weight gradient and one input
+// gradient, and each head BatchNorm layer one apply and one backward descriptor.
 inline int gemm_cap(const cgl_gan_config& c) {
   const int W = co_workers(c), J = c.d.n_layers;
-  return W == 1 ? kMaxGemmDescs : 4 * CGL_MAX_LAYERS + W * (c.epoch * 3 * J + 2 * J);
+  const int hl = co_head_layer(c) > 0 ? c.g.n_layers - co_head_layer(c) : 0;
+  return W == 1 ? kMaxGemmDescs : 4 * CGL_MAX_LAYERS + W * (c.epoch * 3 * J + 2 * J + 3 * hl);
+}
+inline int bn_cap(const cgl_gan_config& c) {
+  return co_head_layer(c) > 0 ? kMaxBnDescs + co_workers(c) * CGL_MAX_LAYERS : kMaxBnDescs;
 }
 inline int head_cap(const cgl_gan_config& c) {
   return co_workers(c) == 1 ? kMaxHeadDescs : co_workers(c) * (CGL_MAX_EPOCH + 1);
@@ -216,6 +264,22 @@ struct WS {
     float* dwpk[CGL_MAX_LAYERS];
     float* dwtpk[CGL_MAX_LAYERS];
   } wk[CGL_MAX_COLOCATED];
+  // co-located Mix-G heads: hk[q] = head q's buffers of the layers >= exchange_layer (hk[0]: the fields above) and
+  // its own G-loss gradient dYL; the layers below keep the one (trunk) set
+  struct Hk {
+    float* gout[CGL_MAX_LAYERS];
+    float* gact[CGL_MAX_LAYERS];
+    float* gpart[CGL_MAX_LAYERS];
+    float* gmean[CGL_MAX_LAYERS];
+    float* ginvstd[CGL_MAX_LAYERS];
+    float* gdA[CGL_MAX_LAYERS];
+    float* gG[CGL_MAX_LAYERS];
+    float* gpk[CGL_MAX_LAYERS];
+    float* wpk[CGL_MAX_LAYERS];
+    float* wtpk[CGL_MAX_LAYERS];
+    float* gGpk[CGL_MAX_LAYERS];
+    float* dYL;
+  } hk[CGL_MAX_COLOCATED];
   int nw;
   int64_t total;
 };
@@ -235,8 +299,8 @@ WS carve_ws(const cgl_gan_config& c, void* base) {
   w.counters = cv.take<unsigned int>(counter_cap(c));
   w.gemm = cv.take<CglGemmDesc>(gemm_cap(c));
   w.head = cv.take<CglHeadDesc>(head_cap(c));
-  w.bnb = cv.take<CglBnBwdDesc>(kMaxBnDescs);
-  w.bna = cv.take<CglBnApplyDesc>(kMaxBnDescs);
+  w.bnb = cv.take<CglBnBwdDesc>(bn_cap(c));
+  w.bna = cv.take<CglBnApplyDesc>(bn_cap(c));
   for (int l = 0; l < L; ++l) {
     const int f = g.dims[l + 1];
     w.gout[l] = cv.take<float>((int64_t)2 * B * f);
@@ -309,6 +373,56 @@ WS carve_ws(const cgl_gan_config& c, void* base) {
       k.dwpk[j] = cv.take<float>(cgl_pk_floats(d.dims[j + 1], d.dims[j]));
       k.dwtpk[j] = cv.take<float>(cgl_pk_floats(d.dims[j], d.dims[j + 1]));
     }
+  }
+  // head 0's buffers are the ones above; the other co-located heads' follow (layers >= exchange_layer), every
+  // head in head 0's order (one offset per head addresses its packed weight copies)
+  WS::Hk& h0 = w.hk[0];
+  h0.dYL = w.dYL;
+  for (int l = 0; l < CGL_MAX_LAYERS; ++l) {
+    h0.gout[l] = w.gout[l];
+    h0.gact[l] = w.gact[l];
+    h0.gpart[l] = w.gpart[l];
+    h0.gmean[l] = w.gmean[l];
+    h0.ginvstd[l] = w.ginvstd[l];
+    h0.gdA[l] = w.gdA[l];
+    h0.gG[l] = w.gG[l];
+    h0.gpk[l] = w.gpk[l];
+    h0.wpk[l] = w.wpk[l];
+    h0.wtpk[l] = w.wtpk[l];
+    h0.gGpk[l] = w.gGpk[l];
+  }
+  const int xl = co_head_layer(c);
+  // (the heads' packed weight copies, head 0's too: one block per head, so that head q's copies lie a constant
+  // offset after head 0's -- cgl_pack_all_grp's addressing)
+  for (int q = 0; q < nw && xl > 0; ++q)
+    for (int l = xl; l < L; ++l) {
+      w.hk[q].wpk[l] = cv.take<float>(cgl_pk_floats(g.dims[l + 1], g.dims[l]));
+      w.hk[q].wtpk[l] = cv.take<float>(cgl_pk_floats(g.dims[l], g.dims[l + 1]));
+    }
+  for (int q = 1; q < nw && xl > 0; ++q) {
+    WS::Hk& k = w.hk[q];
+    const WS::Hk own = k;
+    k = h0;        // (the trunk's layers: shared)
+    for (int l = xl; l < L; ++l) {
+      k.wpk[l] = own.wpk[l];
+      k.wtpk[l] = own.wtpk[l];
+    }
+    for (int l = xl; l < L; ++l) {
+      const int f = g.dims[l + 1];
+      k.gout[l] = cv.take<float>((int64_t)2 * B * f);
+      if (l + 1 < L && g.bn[l]) {
+        k.gact[l] = cv.take<float>((int64_t)2 * B * f);
+        const int64_t tiles = (2 * B + 31) / 32;
+        k.gpart[l] = cv.take<float>(tiles * 2 * f * 2);
+        k.gmean[l] = cv.take<float>((int64_t)2 * f);
+        k.ginvstd[l] = cv.take<float>((int64_t)2 * f);
+        k.gdA[l] = cv.take<float>((int64_t)B * f + kXchgPad);
+        k.gpk[l] = cv.take<float>(cgl_pk_floats(2 * B, f));
+        k.gGpk[l] = cv.take<float>(cgl_pk_floats(B, f));
+      }
+      if (l + 1 < L) k.gG[l] = cv.take<float>((int64_t)B * f + kXchgPad);
+    }
+    k.dYL = cv.take<float>((int64_t)B * g.dims[L] + kXchgPad);
   }
   w.total = cv.off;
   return w;
@@ -554,6 +668,11 @@ struct cgl_gan {
   CglCoShard shard{};                // the sampler's shards
   int64_t shard_row0[CGL_MAX_COLOCATED] = {};
   int plan_err = 0;                  // a grouped launch whose W copies are not the same problem
+  // co-located Mix-G heads (cfg.colocated_heads; xl = the first head layer, 0: off)
+  int xl = 0;
+  GLayout gy;                        // the G buffers: trunk, then the heads (gl below: trunk + head 0)
+  CglOpPack pack_h{};                // head 0's packing jobs, repeated per head (the round prologue, sync_params)
+  CglCoOff hpk_off{};                // head q's packed weight copies, in floats from head 0's
   // parameter tensor pointers
   std::vector<TensorRec> gl, dl;
   int64_t run_mean_off[CGL_MAX_LAYERS], run_var_off[CGL_MAX_LAYERS];
@@ -569,15 +688,22 @@ struct cgl_gan {
 
 namespace {
 
-const float* gparam(const cgl_gan* c, int layer, int kind) {
+// (hd: the co-located Mix-G head whose tensor, for a head layer; the trunk's layers have one copy)
+const float* gparam(const cgl_gan* c, int layer, int kind, int hd = 0) {
   for (auto& t : c->gl)
-    if (t.layer == layer && t.kind == kind) return c->bufs.g_params + t.off;
+    if (t.layer == layer && t.kind == kind)
+      return c->bufs.g_params + t.off + (c->xl > 0 && layer >= c->xl ? hd * c->gy.head_stride : 0);
   return nullptr;
 }
-float* ggrad(const cgl_gan* c, int layer, int kind) {
+float* ggrad(const cgl_gan* c, int layer, int kind, int hd = 0) {
   for (auto& t : c->gl)
-    if (t.layer == layer && t.kind == kind) return c->bufs.g_grads + t.off;
+    if (t.layer == layer && t.kind == kind)
+      return c->bufs.g_grads + t.off + (c->xl > 0 && layer >= c->xl ? hd * c->gy.head_stride : 0);
   return nullptr;
+}
+float* grunning(const cgl_gan* c, int layer, bool var, int hd = 0) {
+  return c->bufs.g_running + (var ? c->run_var_off[layer] : c->run_mean_off[layer]) +
+         (c->xl > 0 && layer >= c->xl ? hd * c->gy.run_stride : 0);
 }
 // (wk: the co-located worker whose model, nd floats after the previous worker's)
 const float* dparam(const cgl_gan* c, int layer, int kind, int wk = 0) {
@@ -774,6 +900,22 @@ void push_bnb(cgl_gan* c, std::vector<Launch>& ph, const CglBnBwdDesc& b) {
   ph.push_back(L);
 }
 
+// the same BatchNorm apply / backward for every co-located Mix-G head as one launch (cgl_bn_apply_grp,
+// cgl_bn_bwd8_grp): bs[q] = head q's descriptor; grid / grid_y as one head's launch has them
+void push_bna_grp(cgl_gan* c, std::vector<Launch>& ph, const std::vector<CglBnApplyDesc>& bs) {
+  push_bna(c, ph, bs[0]);
+  for (size_t q = 1; q < bs.size(); ++q) c->bna.push_back(bs[q]);
+  ph.back().count = ph.back().nw = (int)bs.size();
+}
+void push_bnb_grp(cgl_gan* c, std::vector<Launch>& ph, const std::vector<CglBnBwdDesc>& bs) {
+  push_bnb(c, ph, bs[0]);
+  for (size_t q = 1; q < bs.size(); ++q) c->bnb.push_back(bs[q]);
+  Launch& L = ph.back();
+  L.count = L.nw = (int)bs.size();
+  L.grid_y = L.grid;          // workgroups per head
+  L.grid = L.grid_y * L.nw;
+}
+
 void push_adam(cgl_gan* c, std::vector<Launch>& ph, float* p, float* g, float* m, float* v, long n,
                const float* ss, const float* bc, int tail, const float* scale = nullptr,
                const unsigned int* found = nullptr) {
@@ -952,7 +1094,7 @@ bool plan_pack_carriers(cgl_gan* c, std::vector<Launch>& A) {
   std::vector<Launch*> car;
   bool gfwd_done = false;
   for (auto& L : A) {
-    if (L.kind == K_BNAPPLY && L.layer >= 0) car.push_back(&L);
+    if (L.kind == K_BNAPPLY && L.layer >= 0 && L.nw == 1) car.push_back(&L);   // (not the W-head grouped ones)
     if (L.kind == K_HEAD) gfwd_done = true;
     if (L.kind == K_HEAD && gfwd_done && c->head[L.first].deferred) {
       L.layer = INT_MAX - 1;
@@ -1215,100 +1357,131 @@ int build_plan(cgl_gan* c) {
   // BatchNorm1d(train) + LeakyReLU of a layer's output is a cgl_bn_apply launch between the two GEMMs: it
   // combines the producer GEMM's per-tile partials and writes the activation for the next GEMM and the
   // backward pass.
-  CglBnFwd pend;
-  std::memset(&pend, 0, sizeof(pend));
+  // Co-located Mix-G heads (XL > 0): the layers below XL are the trunk, run once; each layer >= XL is ONE grouped
+  // launch of the NW heads' copies of it -- head q's own weights (gparam(.., q)), buffers (w.hk[q]) and running
+  // statistics -- and its BatchNorm apply one cgl_bn_apply_grp launch.  The first head layer reads the trunk's output.
+  const int NW = c->nw;
+  const int XL = c->xl;
+  auto is_head = [&](int l) { return XL > 0 && l >= XL; };
+  auto HK = [&](int q) -> const WS::Hk& { return w.hk[XL > 0 ? q : 0]; };
+  CglBnFwd pend[CGL_MAX_COLOCATED];
+  std::memset(pend, 0, sizeof(pend));
   bool pend_on = false;
   for (int l = 0; l < L; ++l) {
     const int fi = g.dims[l], fo = g.dims[l + 1];
-    CglGemmDesc e = make_gemm(0, 2 * B, fo, fi);
-    if (l + 1 < L && g.bn[l] && B < 64) choose_tiles(e, 1);  // keep producer tiles <= one call
-    if (l == 0) {
-      e.a = rows(c->z_ahead ? w.znext : c->bufs.z, fi);
-      if (c->z_ahead) {           // the round's z rows copied out to bufs.z as the GEMM loads them
-        e.a_copy = c->bufs.z;
-        e.a_copy_ld = fi;
-        e.a_copy_row0 = 0;
-      }
-    } else {
-      e.a = rows(w.gout[l - 1], fi);
-    }
+    const int nh = is_head(l) ? NW : 1;                  // copies of this layer
+    const bool prev_head = l >= 1 && is_head(l - 1);     // (each head reads its own previous layer)
     // fragment-packed operands (cgl_pk_off): the weights, packed by the round prologue, and the
     // BatchNorm + LeakyReLU output cgl_bn_apply writes packed beside its row-major copy
     const bool pk_on = pack_enabled();
-    if (pk_on && fi >= 256 && c->pack.nj < CGL_PACK_MAXJ) {   // (short-K layers: no gain measured)
-      CglOpPackJob& J = c->pack.j[c->pack.nj++];
-      J.src = gparam(c, l, 0);
-      J.dst = w.wpk[l];
-      J.R = fo;
-      J.K = fi;
-      J.ld = fi;
-      J.trans = 0;
-      c->pack_need.push_back(l);
-      e.b_pk = 1;
+    bool b_pk = false;
+    if (pk_on && fi >= 256) {   // (short-K layers: no gain measured)
+      CglOpPack& P = is_head(l) ? c->pack_h : c->pack;   // (a head layer: head 0's job, repeated per head)
+      if (P.nj < CGL_PACK_MAXJ) {
+        CglOpPackJob& J = P.j[P.nj++];
+        J.src = gparam(c, l, 0);
+        J.dst = HK(0).wpk[l];
+        J.R = fo;
+        J.K = fi;
+        J.ld = fi;
+        J.trans = 0;
+        if (!is_head(l)) c->pack_need.push_back(l);
+        b_pk = true;
+      }
+    }
+    std::vector<CglGemmDesc> grp;
+    std::vector<CglBnApplyDesc> aps;
+    for (int q = 0; q < nh; ++q) {
+      const WS::Hk& hk = HK(q);
+      const WS::Hk& hp = prev_head ? hk : w.hk[0];
+      CglGemmDesc e = make_gemm(0, 2 * B, fo, fi);
+      if (l + 1 < L && g.bn[l] && B < 64) choose_tiles(e, 1);  // keep producer tiles <= one call
+      if (l == 0) {
+        e.a = rows(c->z_ahead ? w.znext : c->bufs.z, fi);
+        if (c->z_ahead) {           // the round's z rows copied out to bufs.z as the GEMM loads them
+          e.a_copy = c->bufs.z;
+          e.a_copy_ld = fi;
+          e.a_copy_row0 = 0;
+        }
+      } else {
+        e.a = rows(hp.gout[l - 1], fi);
+      }
+      e.b_pk = b_pk ? 1 : 0;
+      if (pend_on) {
+        if (q == 0 || prev_head) {
+          CglBnApplyDesc ap;
+          std::memset(&ap, 0, sizeof(ap));
+          ap.F = fi;
+          ap.Y = hp.gout[l - 1];
+          ap.ld_y = fi;
+          ap.act = hp.gact[l - 1];
+          ap.ld_act = fi;
+          ap.bn = pend[prev_head ? q : 0];
+          if (pk_on) ap.act_pk = hp.gpk[l - 1];
+          aps.push_back(ap);
+        }
+        if (pk_on) e.a_pk = 1;
+        e.a = rows(e.a_pk ? hp.gpk[l - 1] : hp.gact[l - 1], fi);
+      }
+      if ((e.a_pk || e.b_pk) && !(l + 1 < L && g.bn[l] && B < 64)) choose_tiles(e);
+      e.a_vec = (fi % 4 == 0) && al16(e.a.p0);
+      e.b = rows(e.b_pk ? hk.wpk[l] : gparam(c, l, 0, q), fi);
+      e.b_vec = (fi % 4 == 0);
+      e.bias = gparam(c, l, 1, q);
+      if (l == L - 1) {
+        e.act = CGL_EPI_ACT_TANH;
+      } else if (g.bn[l]) {
+        e.act = CGL_EPI_ACT_NONE;
+        e.stat_part = hk.gpart[l];
+        e.stat_gr = B;
+      } else {
+        e.act = CGL_EPI_ACT_LEAKY;
+      }
+      e.slope = sl;
+      e.C = hk.gout[l];
+      e.ldc = fo;
+      grp.push_back(e);
     }
     if (pend_on) {
-      CglBnApplyDesc ap;
-      std::memset(&ap, 0, sizeof(ap));
-      ap.F = fi;
-      ap.Y = w.gout[l - 1];
-      ap.ld_y = fi;
-      ap.act = w.gact[l - 1];
-      ap.ld_act = fi;
-      ap.bn = pend;
-      if (pk_on) {
-        ap.act_pk = w.gpk[l - 1];
-        e.a_pk = 1;
+      if (aps.size() == 1) {
+        push_bna(c, A, aps[0]);
+        A.back().layer = l;
+      } else {
+        push_bna_grp(c, A, aps);
       }
-      push_bna(c, A, ap);
-      A.back().layer = l;
-      e.a = rows(e.a_pk ? w.gpk[l - 1] : w.gact[l - 1], fi);
       pend_on = false;
     }
-    if ((e.a_pk || e.b_pk) && !(l + 1 < L && g.bn[l] && B < 64)) choose_tiles(e);
-    e.a_vec = (fi % 4 == 0) && al16(e.a.p0);
-    e.b = rows(e.b_pk ? w.wpk[l] : gparam(c, l, 0), fi);
-    e.b_vec = (fi % 4 == 0);
-    e.bias = gparam(c, l, 1);
-    if (l == L - 1) {
-      e.act = CGL_EPI_ACT_TANH;
-    } else if (g.bn[l]) {
-      e.act = CGL_EPI_ACT_NONE;
-      e.stat_part = w.gpart[l];
-      e.stat_gr = B;
-    } else {
-      e.act = CGL_EPI_ACT_LEAKY;
-    }
-    e.slope = sl;
-    e.C = w.gout[l];
-    e.ldc = fo;
-    push_gemm(c, A, {e});
+    push_gemm(c, A, grp, nh);
     if (l + 1 < L && g.bn[l]) {
-      CglBnFwd& bn = pend;
-      std::memset(&bn, 0, sizeof(bn));
-      bn.part = w.gpart[l];
-      // the producer's row-tile height as pushed
-      bn.part_bm = 32 * c->gemm.back().TM * c->gemm.back().WM;
-      bn.gr = B;
-      bn.mtot = 2 * B;
-      bn.gamma = gparam(c, l, 2);
-      bn.beta = gparam(c, l, 3);
-      bn.eps = cf.bn_eps;
-      bn.momentum = cf.bn_momentum;
-      bn.slope = sl;
-      bn.run_mean = c->bufs.g_running + c->run_mean_off[l];
-      bn.run_var = c->bufs.g_running + c->run_var_off[l];
-      bn.save_mean = w.gmean[l];
-      bn.save_invstd = w.ginvstd[l];
+      for (int q = 0; q < nh; ++q) {
+        const WS::Hk& hk = HK(q);
+        CglBnFwd& bn = pend[q];
+        std::memset(&bn, 0, sizeof(bn));
+        bn.part = hk.gpart[l];
+        // the producer's row-tile height as pushed
+        bn.part_bm = 32 * c->gemm.back().TM * c->gemm.back().WM;
+        bn.gr = B;
+        bn.mtot = 2 * B;
+        bn.gamma = gparam(c, l, 2, q);
+        bn.beta = gparam(c, l, 3, q);
+        bn.eps = cf.bn_eps;
+        bn.momentum = cf.bn_momentum;
+        bn.slope = sl;
+        bn.run_mean = grunning(c, l, false, q);
+        bn.run_var = grunning(c, l, true, q);
+        bn.save_mean = hk.gmean[l];
+        bn.save_invstd = hk.ginvstd[l];
+      }
       pend_on = true;
     }
   }
-  const float* Xd = w.gout[L - 1];
-  const float* Xg = w.gout[L - 1] + (int64_t)B * img;
+  // worker q's generated rows: the one generator's, or its own head's
+  auto Xd = [&](int q) -> const float* { return HK(q).gout[L - 1]; };
+  auto Xg = [&](int q) -> const float* { return HK(q).gout[L - 1] + (int64_t)B * img; };
 
   // ---- local D steps (Worker.train capgan.py:324-341)
   // Co-located workers (NW > 1): every stage below is ONE launch holding the NW workers' copies of it -- worker q's
   // descriptors read its own model (dparam(.., q)), real rows and buffers (w.wk[q]) and the shared G output.
-  const int NW = c->nw;
   const int C = d.dims[J];
   const float combine = cf.loss == CGL_LOSS_CE2 ? 0.5f : 1.0f;
   // the real rows of worker q's local step ep: through the sampler's / the caller's index list, or in order
@@ -1341,10 +1514,10 @@ int build_plan(cgl_gan* c) {
         CglGemmDesc e = make_gemm(0, Md, fo, fi);
         if (j == 0) {
           CglRowSrc r = real_src(q, ep, fi);
-          r.p1 = Xd;
+          r.p1 = Xd(q);
           r.split = Br;
           e.a = r;
-          e.a_vec = (fi % 4 == 0) && al16(r.p0) && al16(Xd);
+          e.a_vec = (fi % 4 == 0) && al16(r.p0) && al16(Xd(q));
           e.a_copy = k.R;
           e.a_copy_ld = fi;
           e.a_copy_row0 = 0;
@@ -1485,14 +1658,17 @@ int build_plan(cgl_gan* c) {
   // ---- G loss through the updated D (capgan.py:343-347) and its input gradient
   // (co-located: worker q's final input gradient goes straight into slot q of the gathered exchange buffer, its G
   // loss into the word after it -- [gradient | G loss | pad], the layout of exchange mode 1)
-  const int64_t xslot = xchg_slot((int64_t)B * img);
+  // (Mix-G heads: the exchanged gradient is that of the first head layer's input, B x dims[XL]; worker q's G-loss
+  // gradient stays its own, w.hk[q].dYL, and feeds its head's backward)
+  const int64_t xn = (int64_t)B * (XL > 0 ? g.dims[XL] : img);
+  const int64_t xslot = xchg_slot(xn);
   for (int j = 0; j + 1 < J; ++j) {
     const int fi = d.dims[j], fo = d.dims[j + 1];
     std::vector<CglGemmDesc> grp;
     for (int q = 0; q < NW; ++q) {
       const WS::Wk& k = w.wk[q];
       CglGemmDesc e = make_gemm(0, B, fo, fi);
-      e.a = rows(j == 0 ? Xg : k.S[j - 1], fi);
+      e.a = rows(j == 0 ? Xg(q) : k.S[j - 1], fi);
       e.a_vec = (fi % 4 == 0);
       e.b = rows(dparam(c, j, 0, q), fi);
       e.b_vec = (fi % 4 == 0);
@@ -1536,7 +1712,7 @@ int build_plan(cgl_gan* c) {
       h.part = k.hpart;
       h.counter = w.counters + q * (CGL_MAX_EPOCH + 1) + CGL_MAX_EPOCH;
       h.loss_out0 = &(st + q)->g_loss_parts[0];
-      if (NW > 1) h.loss_out2 = w.gath + q * xslot + (int64_t)B * img;
+      if (NW > 1) h.loss_out2 = w.gath + q * xslot + xn;
       h.combine = 1.0f;
       h.scale_dev = scaling ? &st->scale[1] : nullptr;
       h.rows_per_wg = kHeadRows;
@@ -1561,9 +1737,9 @@ int build_plan(cgl_gan* c) {
         n.C = k.dS[j - 1];
         n.ldc = d.dims[j];
       } else {
-        n.tanh_ref = Xg;
+        n.tanh_ref = Xg(q);
         n.tanh_ld = img;
-        n.C = NW > 1 ? w.gath + q * xslot : w.dYL;
+        n.C = NW > 1 && XL == 0 ? w.gath + q * xslot : HK(q).dYL;
         n.ldc = img;
       }
       grp.push_back(n);
@@ -1572,11 +1748,18 @@ int build_plan(cgl_gan* c) {
   }
 
   // ---- G backward (Server.train: F_max.backward() capgan.py:258, on the Xg rows)
+  // Co-located Mix-G heads: each head layer's weight-gradient / input-gradient pair is one launch of [NW][2]
+  // descriptors, from worker q's own unweighted G-loss gradient (mixed-gan.py:263-266); the input gradient of layer XL
+  // of worker q goes into slot q of the gathered buffer, cgl_alpha_combine forms the trunk's gradient from the slots
+  // and the trunk backward runs once.
   std::vector<Launch>* ph = &A;
   if (cf.exchange_layer == -1) {
     c->xchg = w.dYL;
     c->xchg_n = (int64_t)B * img;
     ph = &Bp;
+  } else if (XL > 0) {
+    c->xchg = g.bn[XL - 1] ? w.gdA[XL - 1] : w.gG[XL - 1];
+    c->xchg_n = xn;
   }
   if (NW > 1) {     // the local exchange: alpha from the NW losses, dYL = sum_q alpha_q g_q in rank order
     Launch Lc;
@@ -1586,101 +1769,119 @@ int build_plan(cgl_gan* c) {
   }
   // The BatchNorm1d backward of layer l - 1 (with the LeakyReLU' mask of its output) is a cgl_bn_bwd launch
   // between layer l's input-gradient GEMM and layer l - 1's GEMMs.
-  auto gbuf = [&](int l) -> float* { return l == L - 1 ? w.dYL : w.gG[l]; };
   bool gG_packed[CGL_MAX_LAYERS] = {};   // gG[l] has a packed copy (written by cgl_bn_bwd)
   for (int l = L - 1; l >= 0; --l) {
     std::vector<CglGemmDesc> grp;
     const int fi = g.dims[l], fo = g.dims[l + 1];
-    const float* gA = gbuf(l);
-    {
-      const float* prev;
-      if (l == 0)
-        prev = c->bufs.z + (int64_t)B * fi;
-      else if (g.bn[l - 1])
-        prev = w.gact[l - 1] + (int64_t)B * fi;
-      else
-        prev = w.gout[l - 1] + (int64_t)B * fi;
-      CglGemmDesc t = make_gemm(2, fo, fi + 1, B);
-      t.a = rows(gA, fo);
-      t.b = rows(prev, fi);
-      t.b_ones_col = 1;
-      t.C = ggrad(c, l, 0);
-      t.ldc = fi;
-      t.bias_out = ggrad(c, l, 1);
-      if (scaling) t.inf_flag = &st->found[1];
-      grp.push_back(t);
+    const int nh = is_head(l) ? NW : 1;
+    const bool prev_head = l >= 1 && is_head(l - 1);
+    // dA = dZ W_l: NN on the row-major W, or NT on its packed transpose P(W_l^T) (round prologue)
+    // with dZ packed too when cgl_bn_bwd wrote it
+    CglOpPack& PJ = is_head(l) ? c->pack_h : c->pack;    // (a head layer: head 0's job, repeated per head)
+    const bool pk = l >= 1 && pack_enabled() && PJ.nj < CGL_PACK_MAXJ;
+    if (pk) {
+      CglOpPackJob& J = PJ.j[PJ.nj++];
+      J.src = gparam(c, l, 0);
+      J.dst = HK(0).wtpk[l];
+      J.R = fi;
+      J.K = fo;
+      J.ld = fi;
+      J.trans = 1;
+      if (!is_head(l)) c->pack_need.push_back(INT_MAX);
     }
-    if (l >= 1) {
-      // dA = dZ W_l: NN on the row-major W, or NT on its packed transpose P(W_l^T) (round prologue)
-      // with dZ packed too when cgl_bn_bwd wrote it
-      const bool pk = pack_enabled() && c->pack.nj < CGL_PACK_MAXJ;
-      CglGemmDesc n = make_gemm(pk ? 0 : 1, B, fi, fo);
-      n.a = rows(gA, fo);
-      n.a_vec = (fo % 4 == 0);
-      n.b = rows(gparam(c, l, 0), fi);
-      if (pk) {
-        CglOpPackJob& J = c->pack.j[c->pack.nj++];
-        J.src = gparam(c, l, 0);
-        J.dst = w.wtpk[l];
-        J.R = fi;
-        J.K = fo;
-        J.ld = fi;
-        J.trans = 1;
-        c->pack_need.push_back(INT_MAX);
-        n.b = rows(w.wtpk[l], fo);
-        n.b_pk = 1;
-        if (l < L - 1 && gG_packed[l]) {
-          n.a = rows(w.gGpk[l], fo);
-          n.a_pk = 1;
+    for (int q = 0; q < nh; ++q) {
+      const WS::Hk& hk = HK(q);
+      const WS::Hk& hp = prev_head ? hk : w.hk[0];
+      const float* gA = l == L - 1 ? hk.dYL : hk.gG[l];
+      {
+        const float* prev;
+        if (l == 0)
+          prev = c->bufs.z + (int64_t)B * fi;
+        else if (g.bn[l - 1])
+          prev = hp.gact[l - 1] + (int64_t)B * fi;
+        else
+          prev = hp.gout[l - 1] + (int64_t)B * fi;
+        CglGemmDesc t = make_gemm(2, fo, fi + 1, B);
+        t.a = rows(gA, fo);
+        t.b = rows(prev, fi);
+        t.b_ones_col = 1;
+        t.C = ggrad(c, l, 0, q);
+        t.ldc = fi;
+        t.bias_out = ggrad(c, l, 1, q);
+        if (scaling) t.inf_flag = &st->found[1];
+        grp.push_back(t);
+      }
+      if (l >= 1) {
+        CglGemmDesc n = make_gemm(pk ? 0 : 1, B, fi, fo);
+        n.a = rows(gA, fo);
+        n.a_vec = (fo % 4 == 0);
+        n.b = rows(gparam(c, l, 0, q), fi);
+        if (pk) {
+          n.b = rows(hk.wtpk[l], fo);
+          n.b_pk = 1;
+          if (l < L - 1 && gG_packed[l]) {
+            n.a = rows(hk.gGpk[l], fo);
+            n.a_pk = 1;
+          }
+          choose_tiles(n);
         }
-        choose_tiles(n);
+        n.slope = sl;
+        n.ldc = fi;
+        if (!g.bn[l - 1]) {
+          n.mask_ref = hp.gout[l - 1] + (int64_t)B * fi;
+          n.mask_ld = fi;
+        }
+        if (XL > 0 && l == XL)
+          n.C = w.gath + q * xslot;          // worker q's slot of the trunk-gradient exchange
+        else
+          n.C = g.bn[l - 1] ? hp.gdA[l - 1] : hp.gG[l - 1];
+        grp.push_back(n);
       }
-      n.slope = sl;
-      n.ldc = fi;
-      if (g.bn[l - 1]) {
-        n.C = w.gdA[l - 1];
-      } else {
-        n.mask_ref = w.gout[l - 1] + (int64_t)B * fi;
-        n.mask_ld = fi;
-        n.C = w.gG[l - 1];
-      }
-      grp.push_back(n);
     }
-    push_gemm(c, *ph, grp);
+    push_gemm(c, *ph, grp, nh);
     if (l >= 1 && cf.exchange_layer == l) {
       c->xchg = g.bn[l - 1] ? w.gdA[l - 1] : w.gG[l - 1];
       c->xchg_n = (int64_t)B * fi;
       ph = &Bp;
     }
     if (l >= 1 && g.bn[l - 1]) {
-      CglBnBwdDesc b;
-      std::memset(&b, 0, sizeof(b));
-      b.M = B;
-      b.F = fi;
-      b.dA = w.gdA[l - 1];
-      b.ld_da = fi;
-      b.post = w.gact[l - 1] + (int64_t)B * fi;
-      b.ld_post = fi;
-      b.Y = w.gout[l - 1] + (int64_t)B * fi;
-      b.ld_y = fi;
-      b.mean = w.gmean[l - 1] + fi;        // group 1 = the Xg forward call
-      b.invstd = w.ginvstd[l - 1] + fi;
-      b.gamma = gparam(c, l - 1, 2);
-      b.dZ = w.gG[l - 1];
-      b.ld_dz = fi;
-      b.g_gamma = ggrad(c, l - 1, 2);
-      b.g_beta = ggrad(c, l - 1, 3);
-      b.slope = sl;
-      if (scaling) b.inf_flag = &st->found[1];
-      if (pack_enabled() && l - 1 >= 1) {     // the next input-gradient GEMM reads it packed
-        b.dZ_pk = w.gGpk[l - 1];
-        gG_packed[l - 1] = true;
+      std::vector<CglBnBwdDesc> bs;
+      for (int q = 0; q < (prev_head ? NW : 1); ++q) {
+        const WS::Hk& hp = HK(prev_head ? q : 0);
+        CglBnBwdDesc b;
+        std::memset(&b, 0, sizeof(b));
+        b.M = B;
+        b.F = fi;
+        b.dA = hp.gdA[l - 1];
+        b.ld_da = fi;
+        b.post = hp.gact[l - 1] + (int64_t)B * fi;
+        b.ld_post = fi;
+        b.Y = hp.gout[l - 1] + (int64_t)B * fi;
+        b.ld_y = fi;
+        b.mean = hp.gmean[l - 1] + fi;        // group 1 = the Xg forward call
+        b.invstd = hp.ginvstd[l - 1] + fi;
+        b.gamma = gparam(c, l - 1, 2, q);
+        b.dZ = hp.gG[l - 1];
+        b.ld_dz = fi;
+        b.g_gamma = ggrad(c, l - 1, 2, q);
+        b.g_beta = ggrad(c, l - 1, 3, q);
+        b.slope = sl;
+        if (scaling) b.inf_flag = &st->found[1];
+        if (pack_enabled() && l - 1 >= 1) {     // the next input-gradient GEMM reads it packed
+          b.dZ_pk = hp.gGpk[l - 1];
+          gG_packed[l - 1] = true;
+        }
+        bs.push_back(b);
       }
-      push_bnb(c, *ph, b);
+      if (bs.size() == 1)
+        push_bnb(c, *ph, bs[0]);
+      else
+        push_bnb_grp(c, *ph, bs);
     }
   }
-  int64_t ng = 0;
-  param_layout(g, &ng);
+  // one Adam launch over the whole G buffer (Mix-G heads: the trunk and every head, the reference's one
+  // optim.Adam(net_g.parameters()))
+  const int64_t ng = c->gy.total;
   push_adam(c, *ph, c->bufs.g_params, c->bufs.g_grads, c->bufs.g_m, c->bufs.g_v, (long)ng, &st->g_step_size,
             &st->g_bc2sqrt, 1, scaling ? &st->scale[1] : nullptr, scaling ? &st->found[1] : nullptr);
   ph->back().adam.log = w.rlog;   // the round's tail launch writes the round's record
@@ -1704,6 +1905,18 @@ int build_plan(cgl_gan* c) {
       blk += (int)((cgl_pk_floats(J.R, J.K) / 4 + 255) / 256);
     }
     c->pack.blocks = blk;
+    {                                  // the heads' jobs: pack_h.blocks per head, ahead of the prologue's other jobs
+      int hb = 0;
+      for (int q = 0; q < c->pack_h.nj; ++q) {
+        CglOpPackJob& J = c->pack_h.j[q];
+        J.blk_begin = hb;
+        hb += (int)((cgl_pk_floats(J.R, J.K) / 4 + 255) / 256);
+      }
+      c->pack_h.blocks = hb;
+      for (int q = 0; q < NW && XL > 0; ++q) c->hpk_off.d[q] = w.hk[q].wpk[XL] - w.hk[0].wpk[XL];
+      for (auto& Lq : A)
+        if (Lq.kind == K_PROLOGUE) Lq.grid += hb * NW;
+    }
     c->pack_all = c->pack;
     c->pack_g = c->pack;
     std::memset(&c->pack_d, 0, sizeof(c->pack_d));
@@ -1733,7 +1946,7 @@ int build_plan(cgl_gan* c) {
   fuse_prologue(c);
   link_gemm_prefetch(c);
   if ((int)c->gemm.size() > gemm_cap(cf) || (int)c->head.size() > head_cap(cf) ||
-      (int)c->bnb.size() > kMaxBnDescs || (int)c->bna.size() > kMaxBnDescs)
+      (int)c->bnb.size() > bn_cap(cf) || (int)c->bna.size() > bn_cap(cf))
     return CGL_E_SIZE;
   return c->plan_err;
 }
@@ -1780,14 +1993,20 @@ int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s) {
               (long)xchg_slot(c->xchg_n), (long)c->xchg_n, c->xchg);
       break;
     case K_BNAPPLY:
-      if (L.pk >= 0)
+      if (L.nw > 1)
+        klaunch(cgl_bn_apply_grp, dim3(L.grid * L.grid_y * L.nw), dim3(256), 0, s,
+                (const CglBnApplyDesc*)(c->ws.bna + L.first), L.grid, L.grid * L.grid_y);
+      else if (L.pk >= 0)
         klaunch(cgl_bn_apply_pk, dim3(L.grid * L.grid_y + c->carry[L.pk].blocks), dim3(256), 0, s, c->bna[L.first],
                 L.grid, L.grid * L.grid_y, c->carry[L.pk]);
       else
         klaunch(cgl_bn_apply, dim3(L.grid, L.grid_y), dim3(256), 0, s, c->bna[L.first]);
       break;
     case K_BNBWD:
-      klaunch(cgl_bn_bwd8, dim3(L.grid), dim3(256), 0, s, c->bnb[L.first]);
+      if (L.nw > 1)
+        klaunch(cgl_bn_bwd8_grp, dim3(L.grid), dim3(256), 0, s, (const CglBnBwdDesc*)(c->ws.bnb + L.first), L.grid_y);
+      else
+        klaunch(cgl_bn_bwd8, dim3(L.grid), dim3(256), 0, s, c->bnb[L.first]);
       break;
     case K_ADAM:
       if (L.adpk && L.nw > 1)
@@ -1827,7 +2046,7 @@ int exec_launch(cgl_gan* c, const Launch& L, hipStream_t s) {
       if (c->nw > 1) {
         klaunch(cgl_round_prologue_co, dim3(L.grid), dim3(256), 0, s, L.begin, L.nptr, L.nn, c->cfg.seed, L.nb_norm,
                 std::max(L.nb_samp, 1), c->ws.idx, c->cfg.epoch, c->cfg.batch_real, c->cfg.seed ^ 0x5bd1e995ULL,
-                c->shard, c->pack);
+                c->shard, c->pack, c->pack_h, (long)c->gy.head_stride, c->hpk_off);
         break;
       }
       klaunch(cgl_round_prologue, dim3(L.grid), dim3(256), 0, s, L.begin, L.nptr, L.nn, c->cfg.seed,
@@ -1877,8 +2096,9 @@ const char* cgl_version(void) { return CGL_VERSION_STR; }
 
 int64_t cgl_gan_param_count(const cgl_gan_config* cfg, int model) {
   if (!cfg || (model != CGL_MODEL_G && model != CGL_MODEL_D)) return CGL_E_ARG;
+  if (model == CGL_MODEL_G) return g_layout(*cfg).total;
   int64_t n = 0;
-  param_layout(model == CGL_MODEL_G ? cfg->g : cfg->d, &n);
+  param_layout(cfg->d, &n);
   return n;
 }
 
@@ -1886,8 +2106,18 @@ int cgl_gan_param_tensor(const cgl_gan_config* cfg, int model, int idx, int64_t*
                          int* layer, int* kind) {
   if (!cfg || (model != CGL_MODEL_G && model != CGL_MODEL_D)) return CGL_E_ARG;
   auto v = param_layout(model == CGL_MODEL_G ? cfg->g : cfg->d, nullptr);
+  int64_t hoff = 0;
+  if (model == CGL_MODEL_G && co_head_layer(*cfg) > 0 && idx >= 0) {   // trunk, then head 0, head 1, ...
+    const GLayout y = g_layout(*cfg);
+    const int nh = (int)v.size() - y.n_trunk;
+    if (idx >= y.n_trunk + y.heads * nh) return CGL_E_ARG;
+    if (idx >= y.n_trunk) {
+      hoff = (int64_t)((idx - y.n_trunk) / nh) * y.head_stride;
+      idx = y.n_trunk + (idx - y.n_trunk) % nh;
+    }
+  }
   if (idx < 0 || idx >= (int)v.size()) return CGL_E_ARG;
-  if (offset) *offset = v[idx].off;
+  if (offset) *offset = v[idx].off + hoff;
   if (rows_) *rows_ = v[idx].rows;
   if (cols) *cols = v[idx].cols;
   if (layer) *layer = v[idx].layer;
@@ -1897,7 +2127,7 @@ int cgl_gan_param_tensor(const cgl_gan_config* cfg, int model, int idx, int64_t*
 
 int64_t cgl_gan_running_count(const cgl_gan_config* cfg) {
   if (!cfg) return CGL_E_ARG;
-  return running_layout(cfg->g, nullptr, nullptr);
+  return g_layout(*cfg).run_total;
 }
 
 int64_t cgl_gan_workspace_bytes(const cgl_gan_config* cfg) {
@@ -1938,7 +2168,9 @@ static int gan_create(const cgl_gan_config* cfg, const cgl_gan_buffers* bufs, co
   c->cfg = *cfg;
   c->bufs = *bufs;
   c->ws = carve_ws(*cfg, bufs->workspace);
-  c->gl = param_layout(cfg->g, nullptr);
+  c->xl = co_head_layer(*cfg);
+  c->gy = g_layout(*cfg);
+  c->gl = c->gy.one;
   c->dl = param_layout(cfg->d, &c->nd);
   c->nw = co_workers(*cfg);
   c->shard.nw = c->nw;
@@ -2027,6 +2259,9 @@ static void launch_pack_sync(cgl_gan* c, hipStream_t s, bool with_g) {
     return;
   }
   if (with_g && c->pack_g.blocks > 0) hipLaunchKernelGGL(cgl_pack_all, dim3(c->pack_g.blocks), dim3(256), 0, s, c->pack_g);
+  if (with_g && c->pack_h.blocks > 0)      // the Mix-G heads' copies: head 0's jobs, repeated per head
+    hipLaunchKernelGGL(cgl_pack_all_grp, dim3(c->pack_h.blocks * c->nw), dim3(256), 0, s, c->pack_h, c->pack_h.blocks,
+                       (long)c->gy.head_stride, c->hpk_off);
   if (c->pack_d.blocks > 0)
     hipLaunchKernelGGL(cgl_pack_all_grp, dim3(c->pack_d.blocks * c->nw), dim3(256), 0, s, c->pack_d, c->pack_d.blocks,
                        (long)c->nd, c->dpk_off);
@@ -2262,20 +2497,27 @@ int cgl_gan_tensor(cgl_gan* c, int which, float** ptr, int64_t* n) {
   const cgl_mlp_spec& g = c->cfg.g;
   *ptr = nullptr;
   *n = 0;
+  // which + 256 * q: co-located worker q's copy (its D-side buffers; with Mix-G heads its head's buffers of the
+  // layers >= exchange_layer, the trunk's below)
+  const int wq = which >> 8;
+  which &= 255;
+  if (wq < 0 || wq >= c->nw) return CGL_E_ARG;
+  const WS::Hk& hk = c->ws.hk[c->xl > 0 ? wq : 0];
+  const WS::Wk& wk = c->ws.wk[wq];
   if (which == 0) {
-    *ptr = c->ws.gout[L - 1];
+    *ptr = hk.gout[L - 1];
     *n = (int64_t)2 * B * g.dims[L];
   } else if (which == 1) {
-    *ptr = &c->ws.st->g_loss_parts[0];
+    *ptr = &(c->ws.st + wq)->g_loss_parts[0];
     *n = 1;
   } else if (which == 2) {
-    *ptr = c->ws.dYL;
+    *ptr = hk.dYL;
     *n = (int64_t)B * g.dims[L];
   } else if (which == 3) {                          // device sampler: real-row indices [epoch][Br] (int32)
-    *ptr = (float*)c->ws.idx;
+    *ptr = (float*)wk.idx;
     *n = (int64_t)c->cfg.epoch * c->cfg.batch_real;
   } else if (which == 4) {                          // device sampler: real rows per local D step (int32)
-    *ptr = (float*)&c->ws.st->real_rows[0];
+    *ptr = (float*)&(c->ws.st + wq)->real_rows[0];
     *n = c->cfg.epoch;
   } else if (which == 6) {                          // the device round state (CglStepState, raw words)
     *ptr = (float*)c->ws.st;
@@ -2287,30 +2529,30 @@ int cgl_gan_tensor(cgl_gan* c, int which, float** ptr, int64_t* n) {
     *ptr = (float*)c->ws.gemm;
     *n = (int64_t)(c->gemm.size() * sizeof(CglGemmDesc) / 4);
   } else if (which >= 16 && which < 16 + L) {       // gdA[l]: grad w.r.t. BN+LeakyReLU output (Xg rows)
-    *ptr = c->ws.gdA[which - 16];
+    *ptr = hk.gdA[which - 16];
     *n = (int64_t)B * g.dims[which - 16 + 1];
   } else if (which >= 32 && which < 32 + L) {       // gG[l]: grad w.r.t. Linear output (Xg rows)
-    *ptr = c->ws.gG[which - 32];
+    *ptr = hk.gG[which - 32];
     *n = (int64_t)B * g.dims[which - 32 + 1];
   } else if (which >= 48 && which < 48 + L) {       // gact[l]: BN+LeakyReLU output (2B rows)
-    *ptr = c->ws.gact[which - 48];
+    *ptr = hk.gact[which - 48];
     *n = (int64_t)2 * B * g.dims[which - 48 + 1];
   } else if (which >= 64 && which < 64 + L) {       // gout[l]: Linear output (pre-BN) / activation (2B rows)
-    *ptr = c->ws.gout[which - 64];
+    *ptr = hk.gout[which - 64];
     *n = (int64_t)2 * B * g.dims[which - 64 + 1];
   } else if (which >= 80 && which < 80 + L) {       // saved BN batch mean [2][dims[l+1]] (per forward call)
-    *ptr = c->ws.gmean[which - 80];
+    *ptr = hk.gmean[which - 80];
     *n = (int64_t)2 * g.dims[which - 80 + 1];
   } else if (which >= 96 && which < 96 + L) {       // saved BN invstd [2][dims[l+1]]
-    *ptr = c->ws.ginvstd[which - 96];
+    *ptr = hk.ginvstd[which - 96];
     *n = (int64_t)2 * g.dims[which - 96 + 1];
   } else if (which >= 112 && which < 112 + c->cfg.d.n_layers - 1) {   // D-step hidden activation P[j]
     const int j = which - 112;                                        // (Br + B rows, last local D step)
-    *ptr = c->ws.P[j];
+    *ptr = wk.P[j];
     *n = (int64_t)(c->cfg.batch_real + B) * c->cfg.d.dims[j + 1];
   } else if (which >= 128 && which < 128 + c->cfg.d.n_layers - 1) {   // G-loss pass hidden activation S[j]
     const int j = which - 128;                                        // (B rows, through the updated D)
-    *ptr = c->ws.S[j];
+    *ptr = wk.S[j];
     *n = (int64_t)B * c->cfg.d.dims[j + 1];
   } else {
     return CGL_E_ARG;
@@ -2431,7 +2673,7 @@ int cgl_gan_launch_info(cgl_gan* c, int phase, int idx, int* kind, double* flops
   if (kind) *kind = (int)L.kind;
   if (flops) *flops = L.flops;
   if (grid) {   // workgroups dispatched (2-D BatchNorm grids flattened, carried packing blocks included)
-    *grid = L.kind == K_BNAPPLY ? L.grid * L.grid_y : L.grid;
+    *grid = L.kind == K_BNAPPLY ? L.grid * L.grid_y * L.nw : L.grid;
     if ((L.kind == K_BNAPPLY || L.kind == K_HEAD) && L.pk >= 0) *grid += c->carry[L.pk].blocks;
   }
   return CGL_OK;

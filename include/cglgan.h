@@ -102,6 +102,24 @@ typedef struct cgl_gan_config {
    * gather).  Each worker keeps its own round log and round scalars (cgl_gan_read_round_log_worker,
    * cgl_gan_read_stats_worker); the calls without a worker argument report worker 0. */
   int colocated;
+  /* Co-located Mix-G / CGLGAN group (0: off, 1: on): the co-located context's generator is the server's whole
+   * MixGenerator(ims, W) (model/mnist_model.py:32-66, CGLGAN/2DMG/model.py:26-50) -- ONE shared trunk (layers <
+   * exchange_layer), computed once per round, and W heads (layers >= exchange_layer), worker q's head feeding worker
+   * q's discriminator; every head stage of the round is one launch over the W heads.  Requires colocated >= 2,
+   * 1 <= exchange_layer < g.n_layers, loss_scale == 0 and batch * g.dims[exchange_layer] % 4 == 0 (CGL_E_ARG
+   * otherwise); with it 0 a co-located context keeps refusing exchange_layer != -1.  cfg.g describes the trunk plus
+   * ONE head.  Layout of g_params / g_grads / g_m / g_v (cgl_gan_param_count(cfg, CGL_MODEL_G) floats, every tensor
+   * 64-float aligned):
+   *     [trunk tensors | head 0 tensors | head 1 tensors | ... | head W-1 tensors]
+   * in MixGenerator(ims, W).state_dict() parameter order, a constant stride between heads; cgl_gan_param_tensor's
+   * index runs over the trunk, then head 0, head 1, ... (a head tensor reports its layer within cfg.g).  g_running
+   * holds the trunk's running statistics, then each head's (constant stride).  The trunk is a contiguous prefix of
+   * both.  Worker q's head gradient comes from its own unweighted G loss (losses.sum().backward(),
+   * mixed-gan.py:263-266); the gradient of layer exchange_layer's input lands in slot q of the gathered buffer,
+   * cgl_alpha_combine forms sum_q alpha_q g_q in rank order with the configured weighting, the trunk backward runs
+   * once from it, and one Adam launch steps the whole buffer (the reference's one optim.Adam(net_g.parameters())).
+   * cgl_gan_exchange_buffer returns the combined gradient. */
+  int colocated_heads;
 } cgl_gan_config;
 #define CGL_MAX_COLOCATED 16
 
@@ -156,10 +174,12 @@ typedef struct cgl_gan_round_rec {
 } cgl_gan_round_rec;
 
 /* ---------------- layout / sizing queries (host only, no device access) ---------------- */
-/* Number of floats of the flat parameter buffer of G or D (each tensor 256-byte aligned). */
+/* Number of floats of the flat parameter buffer of G or D (each tensor 256-byte aligned).  G of a colocated_heads
+ * context: the trunk plus W heads (cgl_gan_config.colocated_heads); cgl_gan_running_count likewise. */
 int64_t cgl_gan_param_count(const cgl_gan_config* cfg, int model);
 /* Tensor `idx` (reference state-dict order: Linear weight, bias, then BN weight, bias per layer)
- * of G or D: offset in floats and shape.  Returns 0, or CGL_E_ARG past the last tensor. */
+ * of G or D: offset in floats and shape.  Returns 0, or CGL_E_ARG past the last tensor.  G of a colocated_heads
+ * context: idx runs over the trunk's tensors, then head 0's, head 1's, ... (MixGenerator.state_dict() order). */
 int cgl_gan_param_tensor(const cgl_gan_config* cfg, int model, int idx, int64_t* offset, int* rows, int* cols,
                          int* layer, int* kind /* 0 W, 1 b, 2 BN gamma, 3 BN beta */);
 int64_t cgl_gan_running_count(const cgl_gan_config* cfg);
@@ -244,7 +264,10 @@ int cgl_gan_exchange_buffer(cgl_gan* ctx, float** ptr, int64_t* n);
  * 48+l / 64+l = layer l's BN+LeakyReLU output / Linear output [2B][dims[l+1]],
  * 80+l / 96+l = saved BN batch mean / invstd [2][dims[l+1]],
  * 112+j = D hidden layer j's LeakyReLU output of the (last) local D step [Br+B][d.dims[j+1]],
- * 128+j = the same for the G-loss pass through the updated D [B][d.dims[j+1]]. */
+ * 128+j = the same for the G-loss pass through the updated D [B][d.dims[j+1]].
+ * Co-located: `which` + 256 * q selects worker q's copy (q < W; q = 0 as without it): its D-side tensors (1, 3,
+ * 4, 112+j, 128+j) and, with colocated_heads, its head's tensors of the layers >= exchange_layer (0, 2, 16+l ..
+ * 96+l; the trunk's layers and every other code are shared). */
 int cgl_gan_tensor(cgl_gan* ctx, int which, float** ptr, int64_t* n);
 /* Synchronous copy of the round scalars to the host. */
 int cgl_gan_read_stats(cgl_gan* ctx, cgl_gan_stats* out, void* stream);
