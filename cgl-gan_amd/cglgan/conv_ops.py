@@ -423,7 +423,9 @@ def bn2d_fwd(x, n, hw, c, gamma, beta, y, groups=1, eps=0.8, momentum=0.1, runni
 
 
 def bn2d_stats_scratch(c, groups, device):
-    """The zeroed per-BatchNorm scratch of bn2d_fwd_stats (sliced finalize tickets + slice results)."""
+    """The zeroed per-BatchNorm scratch of bn2d_fwd_stats (sliced finalize tickets + slice results).  Zeroed here,
+    once: every launch leaves its tickets at 0 again, so calls of different n / hw may share it as long as they are
+    ordered on one stream."""
     n = C.lib.cgl_bn2d_stats_scratch_bytes(c, groups)
     if n < 0:
         raise RuntimeError(f"bn2d_stats_scratch: bad shape (rc={n})")
@@ -641,7 +643,8 @@ def nhwc_to_nchw(x, y, n, c, hw):
 def dense1_head_nhwc(x, w, b, y, dy, dx, n, c, hw, kind, calls, scratch, flat=None, bn_in=None):
     """adv_layer forward + loss + input gradient in one launch (cgl_dense1_head_nhwc).  ``calls``: [(rows, target,
     weight, loss_out, nvalid)] -- one or two calls over consecutive rows (nvalid: the first call only).
-    ``scratch``: >= n + 16 floats, zeroed once before its first use (a monotonic ticket + the loss terms).
+    ``scratch``: >= n + 16 floats, zeroed once before its first use (a ticket, back at 0 after every launch, + the
+    loss terms); stream-ordered calls of different n may share it.
     ``bn_in`` = (coef, groups): ``x`` is the pre-BatchNorm map, its BatchNorm (bn2d_fwd_stats(coef=)'s scale /
     shift, act none) applied in the loads."""
     coef, groups = bn_in if bn_in is not None else (None, 1)

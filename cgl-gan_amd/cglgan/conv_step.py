@@ -316,7 +316,7 @@ class ConvGanStep:
         self.c1_fuse = os.environ.get("CGL_CONV_C1FUSE", "1") != "0"
         # the D head (adv_layer forward, the loss head(s), adv_layer's input gradient) as ONE launch per pass
         # (cgl_dense1_head_nhwc, bitwise the separate launches; CGL_CONV_HEADFUSE=0 keeps them).  Each pass has its
-        # own scratch: a monotonic ticket counted modulo that launch's grid + the per-row loss terms
+        # own scratch: a ticket (counted up to the launch's grid, reset by its last workgroup) + the per-row loss terms
         self.head_fuse = os.environ.get("CGL_CONV_HEADFUSE", "1") != "0"
         # ... and with it, D's last BatchNorm (model.14) applied in the head's loads (its finalize keeps the scale /
         # shift only: one cgl_eltwise fewer per pass; bitwise, CGL_CONV_HEADBN=0 applies it)

@@ -2566,7 +2566,8 @@ __global__ __launch_bounds__(256) void cgl_bn_finalize(CglBnFinArgs a) {
 // (s, c) merges slice s of channel c's chunks of every call into {mean_s, M2_s} (two passes, fixed
 // order), publishes them with agent-scope atomic stores and takes a ticket; the last block of
 // channel c merges the S slices in slice order (Chan) and finishes exactly as cgl_bn_finalize mode
-// 0.  Tickets are monotonic (the caller zeroes them once; every launch adds S per channel).
+// 0.  The caller zeroes the tickets once; a launch counts a channel's ticket up to S and its last block
+// stores 0 again, so launches that share a scratch (stream-ordered) may differ in S.
 #define CGL_FIN_MAXS 64
 struct CglBnFinSliced {
   CglBnFinArgs f;
@@ -2613,7 +2614,11 @@ __global__ __launch_bounds__(256) void cgl_bn_finalize_sliced(CglBnFinSliced a) 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the published words have landed
     const unsigned int old = __hip_atomic_fetch_add((cgl_gu32*)(a.ctr + c), 1u, __ATOMIC_RELAXED,
                                                     __HIP_MEMORY_SCOPE_AGENT);
-    last = (old % (unsigned)S) == (unsigned)(S - 1);
+    last = old == (unsigned)(S - 1);
+    // every block of the channel has drawn its ticket, so nothing in this launch touches it again: back to 0 at once
+    // (the store overlaps the merge below), and the next launch on this scratch -- stream-ordered after this one --
+    // may cut the channel into another number of slices
+    if (last) __hip_atomic_store((cgl_gu32*)(a.ctr + c), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   if (!last) return;
@@ -2744,7 +2749,7 @@ __global__ __launch_bounds__(256) void cgl_dense1_fwd_nhwc_k(const float* __rest
 // (forward, loss head(s), input gradient) become one.  The calls (the D step's real and fake halves, or the
 // G-loss pass's one call) each keep their own target, weight and batch mean; a short first call (nv) gives its
 // padding rows no loss and a zero gradient.  The batch-mean losses: every wave publishes its row's loss term
-// (agent-scope atomic store), the workgroup takes a monotonic ticket, and the last workgroup to arrive sums
+// (agent-scope atomic store), the workgroup takes a ticket (0 .. grid - 1), and the last workgroup to arrive sums
 // the terms in cgl_adv_loss_at's order (thread t: rows t, t + 256, ... in double; then the 256 partials in
 // order), so every output is bitwise what the three separate launches give.
 struct CglHeadCall {
@@ -2759,7 +2764,7 @@ struct CglDHeadArgs {
   int n, C, hw, loss, ncalls;
   CglHeadCall call[2];
   float* lrow;               // [n] published loss terms
-  unsigned int* ticket;      // monotonic (zeroed once by the caller)
+  unsigned int* ticket;      // zeroed once by the caller; 0 again after every launch
   const float* coef; int groups;   // X's BatchNorm [2][groups][C] applied in the loads (cgl_dense1_row), or null
 };
 __global__ __launch_bounds__(256) void cgl_dense1_head_k(CglDHeadArgs a) {
@@ -2801,7 +2806,11 @@ __global__ __launch_bounds__(256) void cgl_dense1_head_k(CglDHeadArgs a) {
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned int old = __hip_atomic_fetch_add((cgl_gu32*)a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = (old % gridDim.x) == gridDim.x - 1;
+    s_last = old == gridDim.x - 1;
+    // every workgroup has drawn its ticket, so nothing in this launch touches it again: back to 0 at once (the store
+    // overlaps the reduction below), and the next launch on this scratch -- stream-ordered after this one -- may have
+    // another n, hence another grid
+    if (s_last) __hip_atomic_store((cgl_gu32*)a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   if (!s_last) return;
@@ -4950,7 +4959,8 @@ int cgl_bn2d_bwd_stats(const double* part, int R, const float* dY, const float* 
                        int64_t wsb, void* stream) {
   CGL_BATCH_GUARD();
   if (post_coef && (post || groups != 1 || !al16(post_coef) || post_coef_ld % 4)) return CGL_E_ARG;
-  if (colsum_part && (((uintptr_t)colsum_part & 15) || C % 4 || 256 % (C / 4) || ((int64_t)n * hw) % 256))
+  // C < 4 first: 256 % (C / 4) divides by zero for C = 0 (C = 1 .. 3 leave at C % 4)
+  if (colsum_part && (((uintptr_t)colsum_part & 15) || C < 4 || C % 4 || 256 % (C / 4) || ((int64_t)n * hw) % 256))
     return CGL_E_ARG;
   if (!part || !dY || !X || !save_mean || !save_invstd || !gamma || !dX || !ws || !al16(ws)) return CGL_E_ARG;
   if (!al16(dY) || !al16(X) || !al16(dX) || (post && !al16(post)) || (post_out && !al16(post_out))) return CGL_E_ARG;
@@ -5250,7 +5260,8 @@ static int adam_multi_impl(int nt, float* const* p, const float* const* g, float
   a.nt = nt;
   int blk = 0;
   for (int i = 0; i < nt; ++i) {
-    if (!p[i] || !g[i] || !m[i] || !v[i] || n[i] < 0) return CGL_E_ARG;
+    // an empty tensor takes no block; its pointers are not read (torch hands out null for numel() == 0)
+    if (n[i] < 0 || (n[i] > 0 && (!p[i] || !g[i] || !m[i] || !v[i]))) return CGL_E_ARG;
     a.p[i] = p[i]; a.g[i] = g[i]; a.m[i] = m[i]; a.v[i] = v[i]; a.n[i] = (long)n[i];
     a.blk[i] = blk;
     blk += (int)((n[i] + 255) / 256);

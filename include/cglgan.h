@@ -635,7 +635,10 @@ int cgl_bn2d_fwd(const float* X, int n, int hw, int C, int groups, const float* 
 /* cgl_bn2d_fwd (train) from statistics partials already computed (R rows per chunk, the layout of
  * cgl_conv3x3_fwd_packed_stats): finalize + apply only.  scratch (may be null; 256-byte aligned,
  * cgl_bn2d_stats_scratch_bytes, ZEROED ONCE by the caller and kept per BatchNorm layer): lets a call
- * with more than 1024 chunks per forward call finalize in parallel slices (monotonic tickets). */
+ * with more than 1024 chunks per forward call finalize in parallel slices.  Each channel's ticket counts the
+ * slices of one launch and the launch's last block stores 0 again, so the calls that share a scratch may differ
+ * in n, hw and groups (up to the groups the scratch was sized for) -- but they must be ordered on one stream (or
+ * by events): two launches in flight on one scratch mix their tickets and slice results. */
 int64_t cgl_bn2d_stats_scratch_bytes(int C, int groups);
 int cgl_bn2d_fwd_stats(const double* part, int R, const float* X, int n, int hw, int C, int groups, const float* gamma,
                        const float* beta, double eps, double momentum, float* running_mean, float* running_var,
@@ -710,7 +713,9 @@ int cgl_dense1_fwd_nhwc(const float* X, const float* W, const float* b, float* Y
  * of dY -- bitwise what the three (or, with two calls, four) separate launches produce.  Call 0 is rows [0, n0)
  * (target0, weight0, loss_out0, nvalid0: a short first call as cgl_adv_loss), call 1 rows [n0, n) when n0 < n
  * (the D step's real and fake halves, capgan.py:332-340).  scratch: >= n + 16 floats, zeroed ONCE before the first
- * use (its first word is a monotonic ticket; the last workgroup reduces the losses).  in_coef (may be null): X is
+ * use (its first word is a ticket; the last workgroup to arrive reduces the losses and stores 0 to it again, so
+ * later calls on the same scratch may have any n that fits it; calls that share a scratch must be ordered on one
+ * stream or by events).  in_coef (may be null): X is
  * the PRE-BatchNorm map and its BatchNorm2d (act none) is applied to every loaded value, scale in_coef[g c + ch],
  * shift in_coef[in_groups c + g c + ch] for rows of group g = row / (n / in_groups) (cgl_bn2d_fwd_stats_coef's
  * coef; bitwise its applied map, which flat receives).  c % 4 == 0, c * hw % 256 == 0, <= 1024. */
@@ -735,7 +740,8 @@ int cgl_weights_scale(int weighting, int n, int rank, float lam, const float* be
 int cgl_gather_rows(const float* src, const int* idx, int64_t row0, int nrows, int row_floats, float* dst,
                     void* stream);
 /* optim.Adam step `step` over nt (<= 32) tensors (torch _single_tensor_adam op order), host pointer
- * arrays; no host synchronisation. */
+ * arrays; no host synchronisation.  n[i] = 0 is allowed anywhere in the list: that tensor takes no block and its
+ * four pointers are not read (they may be null, as torch's are for an empty tensor). */
 int cgl_adam_multi(int nt, float* const* p, const float* const* g, float* const* m, float* const* v,
                    const int64_t* n, int step, double lr, double beta1, double beta2, double eps, void* stream);
 
@@ -751,7 +757,10 @@ int cgl_normal_fill_dev(float* out, int64_t n, unsigned long long seed, const in
 int cgl_dropout2d_masks_dev(int nm, float* const* masks, const int* n, const int* C, double p,
                             unsigned long long seed, const unsigned long long* counters, const int* round_dev,
                             unsigned long long round_stride, void* stream);
-/* cgl_adam_multi with step = *step_dev + 1 (bias corrections computed on the device) */
+/* cgl_adam_multi with step = *step_dev + 1.  The two bias corrections (lr / (1 - beta1^step) and
+ * sqrt(1 - beta2^step), each rounded to fp32) are computed on the device with the host's double-precision formula;
+ * m and v do not depend on them, and p agrees with cgl_adam_multi(step) up to the rounding of those two values
+ * (bit for bit at steps 1, 2, 10, 1000 and 100000 on the MI355X: tests/test_gpu_conv_state_ops.py). */
 int cgl_adam_multi_dev(int nt, float* const* p, const float* const* g, float* const* m, float* const* v,
                        const int64_t* n, const int* step_dev, double lr, double beta1, double beta2, double eps,
                        void* stream);

@@ -16,32 +16,9 @@ import numpy as np
 import pytest
 import torch
 
+from philox_ref import KAT, M32, philox4x32_10
+
 gpu = pytest.mark.gpu
-
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def philox4x32_10(c, k):
-    """Philox4x32-10 (Salmon et al., SC'11; Random123) on uint32 arrays: c [..., 4] counters, k [..., 2] keys."""
-    c = [np.asarray(c[..., j], dtype=np.uint64) for j in range(4)]
-    k0, k1 = np.asarray(k[..., 0], dtype=np.uint64), np.asarray(k[..., 1], dtype=np.uint64)
-    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
-    w0, w1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
-    for _ in range(10):
-        p0, p1 = m0 * c[0], m1 * c[2]
-        h0, l0, h1, l1 = p0 >> np.uint64(32), p0 & M32, p1 >> np.uint64(32), p1 & M32
-        c = [h1 ^ c[1] ^ k0, l1, h0 ^ c[3] ^ k1, l0]
-        k0, k1 = (k0 + w0) & M32, (k1 + w1) & M32
-    return np.stack(c, axis=-1).astype(np.uint32)
-
-
-# Random123 kat_vectors, philox4x32 10 rounds: (counter, key, output)
-KAT = [
-    ([0, 0, 0, 0], [0, 0], [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8]),
-    ([0xffffffff] * 4, [0xffffffff] * 2, [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]),
-    ([0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344], [0xa4093822, 0x299f31d0],
-     [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1]),
-]
 
 
 def test_philox_known_answers():

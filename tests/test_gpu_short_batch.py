@@ -21,39 +21,10 @@ import pytest
 import torch
 
 from parity_helpers import TRAJ_TOL, make_pair_oracle_only, rel_scalar
+from sampler_ref import M32, _hash, _permute  # noqa: F401  (the Feistel restatement, shared)
 
 pytestmark = pytest.mark.gpu
-M32 = 0xFFFFFFFF
 B, EPOCH, SEED = 64, 2, 20211212
-
-
-def _hash(x, k):
-    x ^= k
-    x = (x * 0x7FEB352D) & M32
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & M32
-    x ^= x >> 16
-    return x
-
-
-def _permute(i, n, key):
-    """cgl_permute (csrc/cgl_common.h): 4-round Feistel on the smallest even bit width >= log2 n,
-    cycle-walked into [0, n)."""
-    bits = 2
-    while (1 << bits) < n:
-        bits += 1
-    bits += bits & 1
-    hb = bits // 2
-    mask = (1 << hb) - 1
-    x = i
-    while True:
-        l, r = x >> hb, x & mask
-        for rnd in range(4):
-            t = l ^ (_hash(r, (key + 0x9E3779B9 * (rnd + 1)) & M32) & mask)
-            l, r = r, t
-        x = (l << hb) | r
-        if x < n:
-            return x
 
 
 def host_sampler(n, br, epoch, rnd, seed):
