@@ -38,7 +38,7 @@ EXPORTS = [
     "cgl_nchw_to_nhwc", "cgl_nhwc_to_nchw", "cgl_dense1_bwd_data_nhwc", "cgl_dense1_fwd_nhwc", "cgl_dense1_head_nhwc", "cgl_adv_loss", "cgl_adam_multi", "cgl_dense_workspace_bytes",
     "cgl_dense_fwd", "cgl_dense_bwd_data", "cgl_dense_bwd_weight", "cgl_gather_rows", "cgl_weights_scale",
     "cgl_conv_packed_floats", "cgl_conv_pack_multi", "cgl_conv_batch_begin", "cgl_conv_batch_end", "cgl_conv_wgrad_defer_begin", "cgl_conv_wgrad_defer_end", "cgl_conv_wgrad_defer_counters", "cgl_conv3x3_bias_by_colsum",
-    "cgl_conv_set_mma_dtype", "cgl_conv_get_mma_dtype",
+    "cgl_conv_set_mma_dtype", "cgl_conv_get_mma_dtype", "cgl_conv_last_launches",
     "cgl_conv_wgrad_defer_cancel", "cgl_conv_wgrad_defer_log", "cgl_conv_round_log", "cgl_conv_round_log_capacity", "cgl_conv_read_round_log", "cgl_conv3x3_fwd_packed", "cgl_conv3x3_bwd_data_packed",
     "cgl_dense_fwd_packed", "cgl_dense_bwd_data_packed", "cgl_conv3x3_stat_chunks", "cgl_conv3x3_fwd_packed_stats",
     "cgl_bn2d_fwd_stats", "cgl_bn2d_fwd_stats_coef", "cgl_conv3x3_fwd_packed_bnin", "cgl_bn2d_stats_scratch_bytes", "cgl_linear_desc_bytes", "cgl_linear_prepare", "cgl_linear_prepare_gather", "cgl_linear_prepare_wgrad_nhwc",
@@ -118,6 +118,24 @@ class ConvRoundLogArgs(ctypes.Structure):
                 ("counters", ctypes.c_void_p), ("n_workers", ctypes.c_int), ("rank", ctypes.c_int),
                 ("weighting", ctypes.c_int), ("half", ctypes.c_float), ("round", ctypes.c_int),
                 ("g_step", ctypes.c_int), ("d_step", ctypes.c_int)]
+
+
+class ConvLaunchRec(ctypes.Structure):
+    """cgl_conv_launch_rec: one launch of the conv path's host dispatch (cgl_conv_last_launches, 48 bytes)."""
+    _fields_ = [(k, ctypes.c_int) for k in ("kernel", "tm", "tn", "wm", "wn", "wk", "flags", "grid", "block",
+                                            "lds_bytes", "np", "splits")]
+
+
+CONV_LAUNCH_REC_MAX = 8     # CGL_CONV_LAUNCH_REC_MAX
+# CGL_K_* (cgl_conv_launch_rec.kernel) in enum order, by the __global__'s name
+CONV_KERNELS = ("none", "cgl_conv_pack", "cgl_conv_fwd", "cgl_conv_fwd_halo", "cgl_conv_n1", "cgl_conv_n1_part",
+                "cgl_conv_n1_tile", "cgl_conv_c1_fwd", "cgl_conv_bwd_n1", "cgl_conv_wgrad", "cgl_conv_wgrad_lds",
+                "cgl_conv_wgrad_n1", "cgl_conv_wgrad_n1t", "cgl_conv_c1_wgrad", "cgl_conv_c1_wgrad_fin",
+                "cgl_conv_wgrad_reduce", "cgl_dense1_wgrad_k", "cgl_chan_reduce", "cgl_chan_reduce4", "cgl_colsum_k",
+                "cgl_bn_finalize", "cgl_bn_finalize_sliced", "cgl_eltwise", "cgl_eltwise1", "cgl_bnb_apply_colsum")
+# CGL_LF_* (cgl_conv_launch_rec.flags), bit i
+CONV_LAUNCH_FLAGS = ("FAST", "BNIN", "LDSM", "HALO", "ROW", "BF16", "STATS_FWD", "STATS_BWD", "NVALID", "BIAS_COL",
+                     "ILV", "STAGE", "DEFERRED")
 
 
 def _hip_runtimes():
@@ -220,6 +238,7 @@ def _load():
         "cgl_conv3x3_bias_by_colsum": (ci, [ci, ci, ci, ci, ci, ci, ci]),
         "cgl_conv_set_mma_dtype": (ci, [ci]),
         "cgl_conv_get_mma_dtype": (ci, []),
+        "cgl_conv_last_launches": (ci, [P(ConvLaunchRec), ci]),
         "cgl_conv_wgrad_defer_begin": (ci, []),
         "cgl_conv_wgrad_defer_end": (ci, [vp]),
         "cgl_conv_wgrad_defer_counters": (ci, [vp, ci, ci, vp, ci]),

@@ -7,6 +7,7 @@ stream (no host synchronisation) and raises on a non-zero return code; there is 
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes
 import functools
@@ -108,6 +109,31 @@ def mma_dtype(dt):
         yield
     finally:
         C.lib.cgl_conv_set_mma_dtype(prev)
+
+
+class Launch(collections.namedtuple("Launch", "kernel tm tn wm wn wk flags grid block lds_bytes np splits")):
+    """One cgl_conv_launch_rec: ``kernel`` is the __global__'s name, ``flags`` a frozenset of CGL_LF_* names
+    ("FAST", "BNIN", "LDSM", "HALO", "ROW", "BF16", "STATS_FWD", "STATS_BWD", "NVALID", "BIAS_COL", "ILV", "STAGE",
+    "DEFERRED")."""
+    __slots__ = ()
+
+
+def last_launches():
+    """What the calling thread's most recent conv3x3_* / dense_* / bn2d_* / act_drop_bwd / colsum_finalize call
+    launched, in order (cgl_conv_last_launches): the record the library's launch sites write, not a model of the
+    dispatch -- tests assert the kernel a case reached with it."""
+    buf = (C.ConvLaunchRec * C.CONV_LAUNCH_REC_MAX)()
+    n = C.lib.cgl_conv_last_launches(buf, C.CONV_LAUNCH_REC_MAX)
+    if n > C.CONV_LAUNCH_REC_MAX:
+        raise RuntimeError(f"cgl_conv_last_launches: {n} launches recorded, {C.CONV_LAUNCH_REC_MAX} kept")
+    out = []
+    for r in buf[:n]:
+        flags = frozenset(name for i, name in enumerate(C.CONV_LAUNCH_FLAGS) if r.flags >> i & 1)
+        if r.flags >> len(C.CONV_LAUNCH_FLAGS) or not 0 < r.kernel < len(C.CONV_KERNELS):
+            raise RuntimeError(f"cgl_conv_last_launches: unknown kernel id {r.kernel} / flags {r.flags:#x}")
+        out.append(Launch(C.CONV_KERNELS[r.kernel], r.tm, r.tn, r.wm, r.wn, r.wk, flags, r.grid, r.block, r.lds_bytes,
+                          r.np, r.splits))
+    return out
 
 
 @contextlib.contextmanager

@@ -1273,6 +1273,59 @@ int cgl_conv_fwd_halo_bf16(bool bnin, int grid, int lds, hipStream_t s, const Cg
 int cgl_conv_wgrad_bf16(int tm, int tn, bool row, bool bnin, int wg, hipStream_t s, const CglConvLaunch& L);
 int cgl_conv_wgrad_lds_bf16(int wm, int ks, bool bnin, int wgl, hipStream_t s, const CglConvLaunch& L);
 
+// ------------------------------------------------------------------------------------------
+// The launch record (cgl_conv_last_launches): every launch site of the conv path stores what it launches, through
+// CGL_LAUNCH -- the kernel's id, its template arguments written out beside the instantiation they name, and the
+// grid / block / LDS expressions of the launch itself (evaluated once, for both).  The record repeats no selection
+// condition: it is filled where the launch is, so it is what was launched.  Host only, per thread.
+void cgl_conv_rec_push(const cgl_conv_launch_rec& r);   // (defined with the host dispatch below)
+void cgl_conv_rec_clear();
+
+// the launch descriptor's own fields (what the kernel is given, not how it was chosen)
+inline int cgl_conv_rec_lflags(const CglConvLaunch& L) {
+  return (L.st_part ? (L.st_mode ? CGL_LF_STATS_BWD : CGL_LF_STATS_FWD) : 0) | (L.st_nv ? CGL_LF_NVALID : 0) |
+         (L.wbias ? CGL_LF_BIAS_COL : 0) | (L.ilv ? CGL_LF_ILV : 0);
+}
+
+inline void cgl_conv_rec_w(int kernel, int tm, int tn, int wm, int wn, int wk, int flags, dim3 grid, dim3 block,
+                           size_t lds, int np, int splits) {
+  cgl_conv_launch_rec r;
+  r.kernel = kernel; r.tm = tm; r.tn = tn; r.wm = wm; r.wn = wn; r.wk = wk; r.flags = flags;
+  r.grid = (int)(grid.x * grid.y * grid.z); r.block = (int)(block.x * block.y * block.z); r.lds_bytes = (int)lds;
+  r.np = np; r.splits = splits;
+  cgl_conv_rec_push(r);
+}
+
+inline void cgl_conv_rec(int kernel, int tm, int tn, int flags, dim3 grid, dim3 block, size_t lds,
+                         const CglConvLaunch* L = nullptr, int splits = 0) {
+  if (L)
+    cgl_conv_rec_w(kernel, tm, tn, L->WM, L->WN, L->WK, flags | cgl_conv_rec_lflags(*L), grid, block, lds, L->np,
+                   splits);
+  else cgl_conv_rec_w(kernel, tm, tn, 0, 0, 0, flags, grid, block, lds, 1, splits);
+}
+
+// record + launch: REC = CGL_REC(kernel id, tm, tn, flags); CGL_LAUNCH_L also takes the launch descriptor (its
+// waves per workgroup, problem count and runtime flags go into the record) and problem 0's pixel splits
+#define CGL_REC(...) __VA_ARGS__
+#define CGL_LAUNCH_L(REC, LP, SPLITS, kern, grid, block, lds, s, ...)  \
+  do {                                                                \
+    const dim3 cgl_g_ = (grid), cgl_b_ = (block);                     \
+    const size_t cgl_l_ = (lds);                                      \
+    cgl_conv_rec(REC, cgl_g_, cgl_b_, cgl_l_, (LP), (SPLITS));        \
+    hipLaunchKernelGGL(kern, cgl_g_, cgl_b_, cgl_l_, s, __VA_ARGS__); \
+  } while (0)
+#define CGL_LAUNCH(REC, kern, grid, block, lds, s, ...) \
+  CGL_LAUNCH_L(CGL_REC(REC), nullptr, 0, kern, grid, block, lds, s, __VA_ARGS__)
+// cgl_conv_wgrad_lds<WM, WN, KS, BNIN, DT>: its waves come from the template (the descriptor's WM / WN / WK are 1)
+#define CGL_LAUNCH_WLDS(WM_, WN_, KS_, BNIN_, DT_, wgl, threads, s, L)                                            \
+  do {                                                                                                          \
+    const dim3 cgl_g_ = dim3(wgl), cgl_b_ = dim3(threads);                                                      \
+    cgl_conv_rec_w(CGL_K_CONV_WGRAD_LDS, 0, 0, WM_, WN_, KS_,                                                   \
+                   (BNIN_ ? CGL_LF_BNIN : 0) | (DT_ == CGL_DTYPE_BF16 ? CGL_LF_BF16 : 0) | cgl_conv_rec_lflags(L), \
+                   cgl_g_, cgl_b_, 0, (L).np, (L).p[0].splits);                                                 \
+    hipLaunchKernelGGL((cgl_conv_wgrad_lds<WM_, WN_, KS_, BNIN_, DT_>), cgl_g_, cgl_b_, 0, s, L);               \
+  } while (0)
+
 #ifndef CGL_CONV_MMA_KERNELS_ONLY
 // ------------------------------------------------------------------------------------------
 // One-output-channel convolution on the vector ALUs (N == 1: Conv2d(64, 1) of the generator's
@@ -2154,9 +2207,9 @@ __global__ __launch_bounds__(256) void cgl_chan_reduce(CglChanArgs a) {
         const int r = min(rb + i * rp, r1 - 1);
         const long o = (long)r * C + c;
         g[i] = gld(a.dY + o);
+        xv[i] = gld(a.X + o);   // (before the sign below reads it, as in cgl_chan_reduce4)
         if (a.psc) g[i] = fmaf(xv[i], a.psc[c], a.psc[a.psc_ld + c]) > 0.f ? g[i] : g[i] * a.slope;
         else if (a.post) g[i] = gld(a.post + o) > 0.f ? g[i] : g[i] * a.slope;
-        xv[i] = gld(a.X + o);
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i)
@@ -2341,9 +2394,11 @@ inline void launch_chan_reduce(const CglChanArgs& a, int nch, hipStream_t s) {
   auto ok = [](const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
   if (a.C % 4 == 0 && a.C >= 4 && a.C <= 256 && 256 % (a.C / 4) == 0 && ok(a.X) && ok(a.dY) && ok(a.post) &&
       ok(a.mean) && !getenv("CGL_CHAN_SCALAR"))
-    hipLaunchKernelGGL(cgl_chan_reduce4, dim3(nch), dim3(256), 0, s, a);
+    CGL_LAUNCH(CGL_REC(CGL_K_CHAN_REDUCE4, a.mode, 0, a.nv ? CGL_LF_NVALID : 0), cgl_chan_reduce4, dim3(nch), dim3(256),
+               0, s, a);
   else
-    hipLaunchKernelGGL(cgl_chan_reduce, dim3(nch), dim3(256), 0, s, a);
+    CGL_LAUNCH(CGL_REC(CGL_K_CHAN_REDUCE, a.mode, 0, a.nv ? CGL_LF_NVALID : 0), cgl_chan_reduce, dim3(nch), dim3(256), 0,
+               s, a);
 }
 
 // Column sums of X [rows][C] per chunk of R rows (any C): part[chunk][c][0] (double); 8 loads in
@@ -3535,6 +3590,23 @@ __global__ __launch_bounds__(256) void cgl_weights_scale_k(CglWeightsArgs a) {
 
 // ==========================================================================================
 // Host side: tap tables, launch planning, C ABI.
+// the launch record of the calling thread's current / most recent entry-point call (cgl_conv_last_launches)
+namespace {
+struct ConvLaunchRecs { int count = 0; cgl_conv_launch_rec r[CGL_CONV_LAUNCH_REC_MAX]; };
+thread_local ConvLaunchRecs t_recs;
+}  // namespace
+void cgl_conv_rec_clear() { t_recs.count = 0; }
+void cgl_conv_rec_push(const cgl_conv_launch_rec& r) {
+  if (t_recs.count < CGL_CONV_LAUNCH_REC_MAX) t_recs.r[t_recs.count] = r;
+  ++t_recs.count;
+}
+// entry of every launching cgl_conv3x3_* / cgl_dense_* / cgl_bn2d_* / cgl_act_drop_bwd* call
+#define CGL_CONV_ENTRY()   \
+  do {                     \
+    cgl_conv_rec_clear();  \
+    CGL_BATCH_GUARD();     \
+  } while (0)
+
 namespace {
 
 // cgl_conv_set_mma_dtype: the calling thread's operand type for the MFMA convolution kernels, read when a
@@ -3817,7 +3889,7 @@ int launch_pack(const float* W, const ConvGeom& g, int transpose, CglConvProb* P
     e += (int64_t)P[i].N * P[i].Kp;
   }
   a.begin[np] = (int)e;
-  hipLaunchKernelGGL(cgl_conv_pack, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, s, a);
+  CGL_LAUNCH(CGL_REC(CGL_K_CONV_PACK, 0, 0, 0), cgl_conv_pack, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
 
@@ -3860,6 +3932,13 @@ bool conv_halo_ok(const CglConvProb* P, int np) {
   }
   return true;
 }
+
+// cgl_conv_fwd<TM, TN, FAST, BNIN, LDSM> on wg workgroups with LDS bytes of LDS (launch_conv_mma's locals), recorded
+// with the template arguments it names
+#define CGL_FWD(TM, TN, FAST, BNIN, LDSM, LDS)                                                              \
+  CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_FWD, TM, TN,                                                             \
+                       (FAST ? CGL_LF_FAST : 0) | (BNIN ? CGL_LF_BNIN : 0) | (LDSM ? CGL_LF_LDSM : 0)),     \
+               &L, 0, (cgl_conv_fwd<TM, TN, FAST, BNIN, LDSM>), dim3(wg), dim3(256), LDS, s, L)
 
 int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float slope, const float* drop,
                     hipStream_t s, double* st_part = nullptr, int st_cpg = 0, const StatBwd* sb = nullptr,
@@ -3904,14 +3983,17 @@ int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float sl
     L.p[0] = P[0];
     const int lds = (CGL_N1T_TH + 2) * (P[0].OW + 2) * P[0].Cin * 4;
     if (P[0].Cin == 64 && P[0].OW == 32 && P[0].YW == 32 && P[0].YH == P[0].OH && !getenv("CGL_N1_TILE")) {
-      hipLaunchKernelGGL(cgl_conv_n1_part, dim3(nimg * ((P[0].OH + CGL_N1P_TH - 1) / CGL_N1P_TH)), dim3(256), 0, s, L);
+      CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_N1_PART, 0, 0, L.in_coef ? CGL_LF_BNIN : 0), &L, 0, cgl_conv_n1_part,
+                   dim3(nimg * ((P[0].OH + CGL_N1P_TH - 1) / CGL_N1P_TH)), dim3(256), 0, s, L);
       return (int)hipGetLastError();
     }
     if (L.in_coef) return CGL_E_ARG;     // the folded BatchNorm input: cgl_conv_n1_part and the MFMA kernels only
     if (P[0].Cin == 64 && P[0].OW == 32)
-      hipLaunchKernelGGL((cgl_conv_n1_tile<16, 32>), dim3(nimg * tiles_y), dim3(256), lds, s, L);
+      CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_N1_TILE, 16, 32, 0), &L, 0, (cgl_conv_n1_tile<16, 32>), dim3(nimg * tiles_y),
+                   dim3(256), lds, s, L);
     else
-      hipLaunchKernelGGL((cgl_conv_n1_tile<0, 0>), dim3(nimg * tiles_y), dim3(256), lds, s, L);
+      CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_N1_TILE, 0, 0, 0), &L, 0, (cgl_conv_n1_tile<0, 0>), dim3(nimg * tiles_y),
+                   dim3(256), lds, s, L);
     return (int)hipGetLastError();
   }
   if (L.in_coef && N == 1) return CGL_E_ARG;
@@ -3924,7 +4006,7 @@ int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float sl
       wg += (P[i].M + per_wg - 1) / per_wg;
       L.p[i] = P[i];
     }
-    hipLaunchKernelGGL(cgl_conv_n1, dim3(wg), dim3(256), 0, s, L);
+    CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_N1, 0, 0, 0), &L, 0, cgl_conv_n1, dim3(wg), dim3(256), 0, s, L);
     return (int)hipGetLastError();
   }
   // the upsampling conv's 4 parity problems from one LDS-staged window per 64-row tile (CGL_CONV_HALO=0: off)
@@ -3940,8 +4022,12 @@ int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float sl
     }
     const int grid = P[0].M / 64 * (N / 64);
     if (bf16) return cgl_conv_fwd_halo_bf16(L.in_coef != nullptr, grid, lds, s, L);
-    if (L.in_coef) hipLaunchKernelGGL((cgl_conv_fwd_halo<true>), dim3(grid), dim3(256), lds, s, L);
-    else hipLaunchKernelGGL((cgl_conv_fwd_halo<false>), dim3(grid), dim3(256), lds, s, L);
+    if (L.in_coef)
+      CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_FWD_HALO, 0, 0, CGL_LF_HALO | CGL_LF_BNIN), &L, 0, (cgl_conv_fwd_halo<true>),
+                   dim3(grid), dim3(256), lds, s, L);
+    else
+      CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_FWD_HALO, 0, 0, CGL_LF_HALO), &L, 0, (cgl_conv_fwd_halo<false>), dim3(grid),
+                   dim3(256), lds, s, L);
     return (int)hipGetLastError();
   }
   const ConvTiling t = conv_tiling_for(P, np);
@@ -3971,9 +4057,9 @@ int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float sl
       if (P[i].Cin != P[0].Cin || P[i].Cin > 512) return CGL_E_ARG;
     if (!fast) return CGL_E_ARG;
     if (bf16) return cgl_conv_fwd_bf16(t.TM, t.TM == 2 ? t.TN : 1, true, true, false, wg, lds, s, L);
-    if (t.TM == 2 && t.TN == 2) hipLaunchKernelGGL((cgl_conv_fwd<2, 2, true, true>), dim3(wg), dim3(256), lds, s, L);
-    else if (t.TM == 2) hipLaunchKernelGGL((cgl_conv_fwd<2, 1, true, true>), dim3(wg), dim3(256), lds, s, L);
-    else hipLaunchKernelGGL((cgl_conv_fwd<1, 1, true, true>), dim3(wg), dim3(256), lds, s, L);
+    if (t.TM == 2 && t.TN == 2) CGL_FWD(2, 2, true, true, false, lds);
+    else if (t.TM == 2) CGL_FWD(2, 1, true, true, false, lds);
+    else CGL_FWD(1, 1, true, true, false, lds);
     return (int)hipGetLastError();
   }
   // the 2 x 2-wave 128 x 128 tiling of a FAST problem: LDS-staged operand panels (CGL_CONV_LDSM=0: the direct
@@ -3983,16 +4069,16 @@ int launch_conv_mma(CglConvProb* P, int np, const float* bias, int act, float sl
   if (bf16)
     return cgl_conv_fwd_bf16(t.TM, t.TM == 2 ? t.TN : 1, fast, false, ldsm, wg, ldsm ? 2 * 2 * 128 * 20 * 4 : lds, s, L);
   if (ldsm) {
-    hipLaunchKernelGGL((cgl_conv_fwd<2, 2, true, false, true>), dim3(wg), dim3(256), 2 * 2 * 128 * 20 * 4, s, L);
+    CGL_FWD(2, 2, true, false, true, 2 * 2 * 128 * 20 * 4);
   } else if (t.TM == 2 && t.TN == 2) {
-    if (fast) hipLaunchKernelGGL((cgl_conv_fwd<2, 2, true>), dim3(wg), dim3(256), lds, s, L);
-    else hipLaunchKernelGGL((cgl_conv_fwd<2, 2, false>), dim3(wg), dim3(256), lds, s, L);
+    if (fast) CGL_FWD(2, 2, true, false, false, lds);
+    else CGL_FWD(2, 2, false, false, false, lds);
   } else if (t.TM == 2) {
-    if (fast) hipLaunchKernelGGL((cgl_conv_fwd<2, 1, true>), dim3(wg), dim3(256), lds, s, L);
-    else hipLaunchKernelGGL((cgl_conv_fwd<2, 1, false>), dim3(wg), dim3(256), lds, s, L);
+    if (fast) CGL_FWD(2, 1, true, false, false, lds);
+    else CGL_FWD(2, 1, false, false, false, lds);
   } else {
-    if (fast) hipLaunchKernelGGL((cgl_conv_fwd<1, 1, true>), dim3(wg), dim3(256), lds, s, L);
-    else hipLaunchKernelGGL((cgl_conv_fwd<1, 1, false>), dim3(wg), dim3(256), lds, s, L);
+    if (fast) CGL_FWD(1, 1, true, false, false, lds);
+    else CGL_FWD(1, 1, false, false, false, lds);
   }
   return (int)hipGetLastError();
 }
@@ -4031,7 +4117,8 @@ int col_sum_part(const float* X, int64_t rows, int C, double* part, float* out, 
   } else {
     const int R = 32;
     nch = (int)((rows + R - 1) / R);
-    hipLaunchKernelGGL(cgl_colsum_k, dim3((C + 255) / 256, nch), dim3(256), 0, s, X, (int)rows, C, R, part);
+    CGL_LAUNCH(CGL_REC(CGL_K_COLSUM, 0, 0, 0), cgl_colsum_k, dim3((C + 255) / 256, nch), dim3(256), 0, s, X, (int)rows, C,
+               R, part);
   }
   std::memset(&f, 0, sizeof(f));
   f.part = part; f.C = C; f.groups = 1; f.chunks_per_group = nch; f.mode = 2; f.dgamma = out;
@@ -4043,7 +4130,8 @@ int col_sum(const float* X, int64_t rows, int C, double* part, float* out, hipSt
   CglBnFinArgs f;
   const int rc = col_sum_part(X, rows, C, part, out, s, f);
   if (rc) return rc;
-  hipLaunchKernelGGL(cgl_bn_finalize, dim3(C), dim3(256), 0, s, f);
+  CGL_LAUNCH(CGL_REC(CGL_K_BN_FINALIZE, f.mode, 0, f.nv ? CGL_LF_NVALID : 0), cgl_bn_finalize, dim3(C), dim3(256), 0, s,
+             f);
   return (int)hipGetLastError();
 }
 
@@ -4110,7 +4198,8 @@ int conv_fwd_impl(const ConvGeom& g, const float* X, const float* W, const float
     a.n = g.n; a.h = g.h; a.w = g.w; a.ho = g.ho; a.wo = g.wo; a.cout = g.cout; a.stride = g.stride;
     a.act = act; a.slope = slope;
     const long npix = (long)g.n * g.ho * g.wo;
-    hipLaunchKernelGGL(cgl_conv_c1_fwd, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
+    CGL_LAUNCH(CGL_REC(CGL_K_CONV_C1_FWD, 0, 0, 0), cgl_conv_c1_fwd, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
+               s, a);
     return (int)hipGetLastError();
   }
   int rc;
@@ -4133,8 +4222,9 @@ int conv_bwd_data_impl(const ConvGeom& g, const float* dY, const float* W, float
   if (!st_part && W && g.cout == 1 && g.cin == 64 && g.ks == 3 && g.stride == 1 && !g.up && al16(dX) &&
       (int64_t)g.n * g.h * g.w < (int64_t)1 << 30) {
     const int npix = g.n * g.h * g.w;
-    hipLaunchKernelGGL((cgl_conv_bwd_n1<16>), dim3((npix + 16 * CGL_BN1_PPT - 1) / (16 * CGL_BN1_PPT)), dim3(256), 0, s, dY, W, dX, npix, g.h, g.w,
-                       CglN1Stats{});
+    CGL_LAUNCH(CGL_REC(CGL_K_CONV_BWD_N1, 16, 0, 0), (cgl_conv_bwd_n1<16>),
+               dim3((npix + 16 * CGL_BN1_PPT - 1) / (16 * CGL_BN1_PPT)), dim3(256), 0, s, dY, W, dX, npix, g.h, g.w,
+               CglN1Stats{});
     return (int)hipGetLastError();
   }
   CglConvProb P[CGL_CONV_MAXP];
@@ -4200,6 +4290,14 @@ struct WgradDefer {
 };
 thread_local WgradDefer t_wdefer;
 
+// cgl_conv_wgrad<TM, TN, ROW, BNIN> on wg workgroups, cgl_conv_wgrad_n1t<...> on one workgroup per pixel split
+// (conv_bwd_weight_impl's locals), recorded with the template arguments they name
+#define CGL_WG(TM, TN, ROW, BNIN)                                                                          \
+  CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_WGRAD, TM, TN, (ROW ? CGL_LF_ROW : 0) | (BNIN ? CGL_LF_BNIN : 0)), &L,  \
+               L.p[0].splits, (cgl_conv_wgrad<TM, TN, ROW, BNIN>), dim3(wg), dim3(256), 0, s, L)
+#define CGL_N1T(REC, SPLITS, ...) \
+  CGL_LAUNCH_L(CGL_REC(REC), &L, SPLITS, (cgl_conv_wgrad_n1t<__VA_ARGS__>), dim3(SPLITS), dim3(256), 0, s, L)
+
 int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, float* dW, float* db, void* ws,
                          int64_t wsb, hipStream_t s, const BnIn* bi = nullptr, const float* ad_post = nullptr,
                          const float* ad_drop = nullptr, float ad_slope = 0.f) {
@@ -4219,14 +4317,15 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
     a.nblk = (int)((npix + a.chunk - 1) / a.chunk);
     if ((int64_t)a.nblk * g.cout * 10 * 4 > wsb) return CGL_E_SIZE;
     a.part = (float*)ws;
-    hipLaunchKernelGGL(cgl_conv_c1_wgrad, dim3(a.nblk), dim3(256), 0, s, a);
+    CGL_LAUNCH(CGL_REC(CGL_K_CONV_C1_WGRAD, 0, 0, 0), cgl_conv_c1_wgrad, dim3(a.nblk), dim3(256), 0, s, a);
     if (t_wdefer.on && !t_wdefer.has_c1) {   // the finish rides in the deferred reductions' launch
       t_wdefer.m.c1 = a;
       t_wdefer.m.c1_blocks = g.cout * 10;
       t_wdefer.has_c1 = true;
+      cgl_conv_rec(CGL_K_CONV_C1_WGRAD_FIN, 0, 0, CGL_LF_DEFERRED, dim3(g.cout * 10), dim3(256), 0);
       return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(cgl_conv_c1_wgrad_fin, dim3(g.cout * 10), dim3(256), 0, s, a);
+    CGL_LAUNCH(CGL_REC(CGL_K_CONV_C1_WGRAD_FIN, 0, 0, 0), cgl_conv_c1_wgrad_fin, dim3(g.cout * 10), dim3(256), 0, s, a);
     return (int)hipGetLastError();
   }
   const bool bf16 = conv_mma_dtype(g) == CGL_DTYPE_BF16;   // the MFMA kernels' operand type (vector kernels: fp32)
@@ -4298,14 +4397,14 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
     if (bf16) {
       if ((rc = cgl_conv_wgrad_lds_bf16(lwm, bi ? 1 : ks, bi != nullptr, wgl, s, L))) return rc;
     } else if (bi) {
-      if (lwm == 2) hipLaunchKernelGGL((cgl_conv_wgrad_lds<2, 2, 1, true>), dim3(wgl), dim3(256), 0, s, L);
-      else hipLaunchKernelGGL((cgl_conv_wgrad_lds<1, 4, 1, true>), dim3(wgl), dim3(256), 0, s, L);
+      if (lwm == 2) CGL_LAUNCH_WLDS(2, 2, 1, true, CGL_DTYPE_F32, wgl, 256, s, L);
+      else CGL_LAUNCH_WLDS(1, 4, 1, true, CGL_DTYPE_F32, wgl, 256, s, L);
     } else if (ks == 2) {
-      if (lwm == 2) hipLaunchKernelGGL((cgl_conv_wgrad_lds<2, 2, 2>), dim3(wgl), dim3(512), 0, s, L);
-      else hipLaunchKernelGGL((cgl_conv_wgrad_lds<1, 4, 2>), dim3(wgl), dim3(512), 0, s, L);
+      if (lwm == 2) CGL_LAUNCH_WLDS(2, 2, 2, false, CGL_DTYPE_F32, wgl, 512, s, L);
+      else CGL_LAUNCH_WLDS(1, 4, 2, false, CGL_DTYPE_F32, wgl, 512, s, L);
     } else {
-      if (lwm == 2) hipLaunchKernelGGL((cgl_conv_wgrad_lds<2, 2, 1>), dim3(wgl), dim3(256), 0, s, L);
-      else hipLaunchKernelGGL((cgl_conv_wgrad_lds<1, 4, 1>), dim3(wgl), dim3(256), 0, s, L);
+      if (lwm == 2) CGL_LAUNCH_WLDS(2, 2, 1, false, CGL_DTYPE_F32, wgl, 256, s, L);
+      else CGL_LAUNCH_WLDS(1, 4, 1, false, CGL_DTYPE_F32, wgl, 256, s, L);
     }
   }
   else if (bi && valu && !(n1t && pl.P[0].Cin == 64 && pl.P[0].XW == 32 && pl.P[0].XH == 32 &&
@@ -4317,14 +4416,14 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
     if (bf16) {
       if ((rc = cgl_conv_wgrad_bf16(pl.t.TM, pl.t.TN, wgrad_row_ok(pl), true, wg, s, L))) return rc;
     } else if (wgrad_row_ok(pl)) {
-      if (pl.t.TM == 2 && pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 2, true, true>), dim3(wg), dim3(256), 0, s, L);
-      else if (pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<1, 2, true, true>), dim3(wg), dim3(256), 0, s, L);
-      else if (pl.t.TM == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 1, true, true>), dim3(wg), dim3(256), 0, s, L);
-      else hipLaunchKernelGGL((cgl_conv_wgrad<1, 1, true, true>), dim3(wg), dim3(256), 0, s, L);
-    } else if (pl.t.TM == 2 && pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 2, false, true>), dim3(wg), dim3(256), 0, s, L);
-    else if (pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<1, 2, false, true>), dim3(wg), dim3(256), 0, s, L);
-    else if (pl.t.TM == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 1, false, true>), dim3(wg), dim3(256), 0, s, L);
-    else hipLaunchKernelGGL((cgl_conv_wgrad<1, 1, false, true>), dim3(wg), dim3(256), 0, s, L);
+      if (pl.t.TM == 2 && pl.t.TN == 2) CGL_WG(2, 2, true, true);
+      else if (pl.t.TN == 2) CGL_WG(1, 2, true, true);
+      else if (pl.t.TM == 2) CGL_WG(2, 1, true, true);
+      else CGL_WG(1, 1, true, true);
+    } else if (pl.t.TM == 2 && pl.t.TN == 2) CGL_WG(2, 2, false, true);
+    else if (pl.t.TN == 2) CGL_WG(1, 2, false, true);
+    else if (pl.t.TM == 2) CGL_WG(2, 1, false, true);
+    else CGL_WG(1, 1, false, true);
   }
   else if (n1t)
   {
@@ -4337,31 +4436,32 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
       // one pixel per slot and step, dY window in LDS: 105 -> 57 us for the B=256 G Conv2d(64, 1)
       // (two / four pixels per step: 77 / 119 us; no staging: 90 us)
       if (bi && stage)
-        hipLaunchKernelGGL((cgl_conv_wgrad_n1t<16, 32, 32, 1, 9216, 512, true>), dim3(P0.splits), dim3(256), 0, s, L);
+        CGL_N1T(CGL_REC(CGL_K_CONV_WGRAD_N1T, 1, 32, CGL_LF_STAGE | CGL_LF_BNIN), P0.splits, 16, 32, 32, 1, 9216, 512, true);
       else if (bi)
-        hipLaunchKernelGGL((cgl_conv_wgrad_n1t<16, 32, 32, 1, 9216, 0, true>), dim3(P0.splits), dim3(256), 0, s, L);
+        CGL_N1T(CGL_REC(CGL_K_CONV_WGRAD_N1T, 1, 32, CGL_LF_BNIN), P0.splits, 16, 32, 32, 1, 9216, 0, true);
       else if (stage)
-        hipLaunchKernelGGL((cgl_conv_wgrad_n1t<16, 32, 32, 1, 9216, 512>), dim3(P0.splits), dim3(256), 0, s, L);
-      else hipLaunchKernelGGL((cgl_conv_wgrad_n1t<16, 32, 32, 1, 9216, 0>), dim3(P0.splits), dim3(256), 0, s, L);
+        CGL_N1T(CGL_REC(CGL_K_CONV_WGRAD_N1T, 1, 32, CGL_LF_STAGE), P0.splits, 16, 32, 32, 1, 9216, 512);
+      else CGL_N1T(CGL_REC(CGL_K_CONV_WGRAD_N1T, 1, 32, 0), P0.splits, 16, 32, 32, 1, 9216, 0);
     }
     else
-      hipLaunchKernelGGL((cgl_conv_wgrad_n1t<0, 0, 0, 2, 16384, 0>), dim3(pl.P[0].splits), dim3(256), 0, s, L);
+      CGL_N1T(CGL_REC(CGL_K_CONV_WGRAD_N1T, 2, 0, 0), pl.P[0].splits, 0, 0, 0, 2, 16384, 0);
   }
   else if (valu)
-    hipLaunchKernelGGL(cgl_conv_wgrad_n1, dim3((pl.P[0].K + 255) / 256, pl.P[0].splits), dim3(256), 0, s, L);
+    CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_WGRAD_N1, 0, 0, 0), &L, pl.P[0].splits, cgl_conv_wgrad_n1,
+                 dim3((pl.P[0].K + 255) / 256, pl.P[0].splits), dim3(256), 0, s, L);
   else if (bf16) {
     if ((rc = cgl_conv_wgrad_bf16(pl.t.TM, pl.t.TN, wgrad_row_ok(pl), false, wg, s, L))) return rc;
   }
   else if (wgrad_row_ok(pl)) {
-    if (pl.t.TM == 2 && pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 2, true>), dim3(wg), dim3(256), 0, s, L);
-    else if (pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<1, 2, true>), dim3(wg), dim3(256), 0, s, L);
-    else if (pl.t.TM == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 1, true>), dim3(wg), dim3(256), 0, s, L);
-    else hipLaunchKernelGGL((cgl_conv_wgrad<1, 1, true>), dim3(wg), dim3(256), 0, s, L);
+    if (pl.t.TM == 2 && pl.t.TN == 2) CGL_WG(2, 2, true, false);
+    else if (pl.t.TN == 2) CGL_WG(1, 2, true, false);
+    else if (pl.t.TM == 2) CGL_WG(2, 1, true, false);
+    else CGL_WG(1, 1, true, false);
   }
-  else if (pl.t.TM == 2 && pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 2>), dim3(wg), dim3(256), 0, s, L);
-  else if (pl.t.TN == 2) hipLaunchKernelGGL((cgl_conv_wgrad<1, 2>), dim3(wg), dim3(256), 0, s, L);
-  else if (pl.t.TM == 2) hipLaunchKernelGGL((cgl_conv_wgrad<2, 1>), dim3(wg), dim3(256), 0, s, L);
-  else hipLaunchKernelGGL((cgl_conv_wgrad<1, 1>), dim3(wg), dim3(256), 0, s, L);
+  else if (pl.t.TM == 2 && pl.t.TN == 2) CGL_WG(2, 2, false, false);
+  else if (pl.t.TN == 2) CGL_WG(1, 2, false, false);
+  else if (pl.t.TM == 2) CGL_WG(2, 1, false, false);
+  else CGL_WG(1, 1, false, false);
   if ((rc = (int)hipGetLastError())) return rc;
   const long nred = (long)g.cout * g.ks * g.ks * g.cin;
   // elements per block: >= ~512 blocks when possible; the rest of the block's threads split the splits
@@ -4377,15 +4477,19 @@ int conv_bwd_weight_impl(const ConvGeom& g, const float* dY, const float* X, flo
     m.r[m.n] = r;
     m.begin[m.n + 1] = m.begin[m.n] + r.wblocks + bblocks;
     ++m.n;
+    cgl_conv_rec(CGL_K_CONV_WGRAD_REDUCE, 0, 0, CGL_LF_DEFERRED | (r.db ? CGL_LF_BIAS_COL : 0),
+                 dim3((unsigned)(r.wblocks + bblocks)), dim3(256), 0, nullptr, r.splits[0]);
     if (db && !bias_col) {   // the bias gradient's column-sum pass now, its finish with the reductions
       double* bp = (double*)(((uintptr_t)part + 255) & ~(uintptr_t)255);
       CglBnFinArgs f;
       if ((rc = col_sum_part(dY, (int64_t)g.n * g.ho * g.wo, g.cout, bp, db, s, f))) return rc;
       t_wdefer.add_fin(f);
+      cgl_conv_rec(CGL_K_BN_FINALIZE, f.mode, 0, CGL_LF_DEFERRED, dim3(f.C), dim3(256), 0);
     }
     return 0;
   }
-  hipLaunchKernelGGL(cgl_conv_wgrad_reduce, dim3((unsigned)(r.wblocks + bblocks)), dim3(256), 0, s, r);
+  CGL_LAUNCH_L(CGL_REC(CGL_K_CONV_WGRAD_REDUCE, 0, 0, r.db ? CGL_LF_BIAS_COL : 0), nullptr, r.splits[0],
+               cgl_conv_wgrad_reduce, dim3((unsigned)(r.wblocks + bblocks)), dim3(256), 0, s, r);
   if ((rc = (int)hipGetLastError())) return rc;
   if (db && !bias_col) {
     double* bp = (double*)(((uintptr_t)part + 255) & ~(uintptr_t)255);
@@ -4418,7 +4522,7 @@ int cgl_conv3x3_bias_by_colsum(int n, int h, int w, int cin, int cout, int strid
 int cgl_conv3x3_fwd(const float* X, const float* W, const float* bias, float* Y, int n, int h, int w, int cin,
                     int cout, int stride, int up, int act, float slope, const float* drop, void* ws, int64_t wsb,
                     void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4427,7 +4531,7 @@ int cgl_conv3x3_fwd(const float* X, const float* W, const float* bias, float* Y,
 
 int cgl_conv3x3_bwd_data(const float* dY, const float* W, float* dX, int n, int h, int w, int cin, int cout,
                          int stride, int up, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4436,7 +4540,7 @@ int cgl_conv3x3_bwd_data(const float* dY, const float* W, float* dX, int n, int 
 
 int cgl_conv3x3_bwd_weight(const float* dY, const float* X, float* dW, float* db, int n, int h, int w, int cin,
                            int cout, int stride, int up, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4446,7 +4550,7 @@ int cgl_conv3x3_bwd_weight(const float* dY, const float* X, float* dW, float* db
 int cgl_conv3x3_bwd_weight_actdrop(const float* dY, const float* post, const float* drop, float slope, const float* X,
                                    float* dW, float* db, int n, int h, int w, int cin, int cout, int stride, int up,
                                    void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4457,7 +4561,7 @@ int cgl_conv3x3_bwd_weight_actdrop(const float* dY, const float* post, const flo
 int cgl_conv3x3_bwd_weight_bnin(const float* dY, const float* X, float* dW, float* db, int n, int h, int w, int cin,
                                 int cout, int stride, int up, const float* in_coef, int in_groups, int in_group,
                                 int in_act, float in_slope, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4484,7 +4588,7 @@ int64_t cgl_dense_workspace_bytes(int M, int K, int N) {
 
 int cgl_dense_fwd(const float* X, const float* W, const float* b, float* Y, int M, int K, int N, int act, float slope,
                   void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(M, 1, 1, K, N, 1, 0, g, 1);
   if (rc) return rc;
@@ -4493,7 +4597,7 @@ int cgl_dense_fwd(const float* X, const float* W, const float* b, float* Y, int 
 
 int cgl_dense_bwd_data(const float* dY, const float* W, float* dX, int M, int K, int N, void* ws, int64_t wsb,
                        void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(M, 1, 1, K, N, 1, 0, g, 1);
   if (rc) return rc;
@@ -4502,7 +4606,7 @@ int cgl_dense_bwd_data(const float* dY, const float* W, float* dX, int M, int K,
 
 int cgl_dense_bwd_weight(const float* dY, const float* X, float* dW, float* db, int M, int K, int N, void* ws,
                          int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(M, 1, 1, K, N, 1, 0, g, 1);
   if (rc) return rc;
@@ -4513,10 +4617,11 @@ int cgl_dense_bwd_weight(const float* dY, const float* X, float* dW, float* db, 
       CglWgradReduceMulti& m = t_wdefer.m;
       m.d1_dy = dY; m.d1_x = X; m.d1_dw = dW; m.d1_db = db; m.d1_M = M; m.d1_K = K;
       m.d1_blocks = (K + 15) / 16 + 1;
+      cgl_conv_rec(CGL_K_DENSE1_WGRAD, 0, 0, CGL_LF_DEFERRED, dim3(m.d1_blocks), dim3(256), 0);
       return CGL_OK;
     }
-    hipLaunchKernelGGL(cgl_dense1_wgrad_k, dim3((K + 15) / 16 + 1), dim3(256), 0, (hipStream_t)stream, dY, X, dW, db,
-                       M, K);
+    CGL_LAUNCH(CGL_REC(CGL_K_DENSE1_WGRAD, 0, 0, 0), cgl_dense1_wgrad_k, dim3((K + 15) / 16 + 1), dim3(256), 0,
+               (hipStream_t)stream, dY, X, dW, db, M, K);
     return (int)hipGetLastError();
   }
   return conv_bwd_weight_impl(g, dY, X, dW, db, ws, wsb, (hipStream_t)stream);
@@ -4540,6 +4645,12 @@ int cgl_conv_set_mma_dtype(int dtype) {
 }
 
 int cgl_conv_get_mma_dtype(void) { return t_mma_dtype; }
+
+int cgl_conv_last_launches(cgl_conv_launch_rec* out, int max) {
+  const int stored = std::min(t_recs.count, CGL_CONV_LAUNCH_REC_MAX);
+  for (int i = 0; out && i < std::min(stored, max); ++i) out[i] = t_recs.r[i];
+  return t_recs.count;
+}
 
 int cgl_conv_wgrad_defer_begin(void) {
   if (t_wdefer.on) return CGL_E_STATE;
@@ -4702,7 +4813,7 @@ int cgl_conv_pack_multi(int njobs, const CglConvPackJob* jobs, void* stream) {
 int cgl_conv3x3_fwd_packed(const float* X, const float* Wp, const float* bias, float* Y, int n, int h, int w, int cin,
                            int cout, int stride, int up, int act, float slope, const float* drop, void* ws,
                            int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4720,7 +4831,7 @@ int64_t cgl_conv3x3_stat_chunks(int n, int h, int w, int cin, int cout, int stri
 int cgl_conv3x3_fwd_packed_stats(const float* X, const float* Wp, const float* bias, float* Y, int n, int h, int w,
                                  int cin, int cout, int stride, int up, int act, float slope, const float* drop,
                                  int groups, double* part, const int* nvalid, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4733,7 +4844,7 @@ int cgl_conv3x3_fwd_packed_bnin(const float* X, const float* Wp, const float* bi
                                 int cin, int cout, int stride, int up, int act, float slope, const float* drop,
                                 int groups, double* part, const float* in_coef, int in_groups, int in_act,
                                 float in_slope, const int* nvalid, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4760,7 +4871,7 @@ int cgl_conv3x3_bwd_data_packed_stats(const float* dY, const float* Wp, float* d
                                       int cout, int stride, int up, int groups, double* part, const float* bn_x,
                                       const float* bn_post, const float* bn_post_coef, int bn_post_coef_ld,
                                       const float* bn_mean, float slope, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4775,7 +4886,7 @@ int cgl_conv3x3_bwd_data_stats(const float* dY, const float* W, float* dX, int n
                                int stride, int up, int groups, double* part, const float* bn_x, const float* bn_post,
                                const float* bn_post_coef, int bn_post_coef_ld, const float* bn_mean, float slope,
                                void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4792,14 +4903,14 @@ int cgl_conv3x3_bwd_data_stats(const float* dY, const float* W, float* dX, int n
   CglN1Stats st;
   st.X = bn_x; st.post = bn_post; st.psc = bn_post_coef; st.psc_ld = bn_post_coef_ld; st.mean = bn_mean;
   st.slope = slope; st.gr = (int)gr; st.part = part;
-  hipLaunchKernelGGL((cgl_conv_bwd_n1<16, true>), dim3(npix / (16 * CGL_BN1_PPT)), dim3(256), 0, (hipStream_t)stream,
-                     dY, W, dX, npix, g.h, g.w, st);
+  CGL_LAUNCH(CGL_REC(CGL_K_CONV_BWD_N1, 16, 0, CGL_LF_STATS_BWD), (cgl_conv_bwd_n1<16, true>),
+             dim3(npix / (16 * CGL_BN1_PPT)), dim3(256), 0, (hipStream_t)stream, dY, W, dX, npix, g.h, g.w, st);
   return (int)hipGetLastError();
 }
 
 int cgl_conv3x3_bwd_data_packed(const float* dY, const float* W, const float* Wp, float* dX, int n, int h, int w,
                                 int cin, int cout, int stride, int up, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(n, h, w, cin, cout, stride, up, g);
   if (rc) return rc;
@@ -4809,7 +4920,7 @@ int cgl_conv3x3_bwd_data_packed(const float* dY, const float* W, const float* Wp
 
 int cgl_dense_fwd_packed(const float* X, const float* Wp, const float* b, float* Y, int M, int K, int N, int act,
                          float slope, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(M, 1, 1, K, N, 1, 0, g, 1);
   if (rc) return rc;
@@ -4819,7 +4930,7 @@ int cgl_dense_fwd_packed(const float* X, const float* Wp, const float* b, float*
 
 int cgl_dense_bwd_data_packed(const float* dY, const float* Wp, float* dX, int M, int K, int N, void* ws, int64_t wsb,
                               void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   ConvGeom g;
   const int rc = conv_geom(M, 1, 1, K, N, 1, 0, g, 1);
   if (rc) return rc;
@@ -4838,7 +4949,7 @@ int64_t cgl_bn2d_workspace_bytes(int n, int hw, int C, int groups) {
 int cgl_bn2d_fwd(const float* X, int n, int hw, int C, int groups, const float* gamma, const float* beta, double eps,
                  double momentum, float* running_mean, float* running_var, int train, int act, float slope, float* Y,
                  float* save_mean, float* save_invstd, const int* nvalid, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   if (!X || !Y || !gamma || !beta || !ws || !al16(ws) || !al16(X) || !al16(Y)) return CGL_E_ARG;
   if (n < 1 || hw < 1 || C % 4 != 0 || !pow2_le256(C) || groups < 1 || n % groups || (act != 0 && act != 1))
     return CGL_E_ARG;
@@ -4871,13 +4982,15 @@ int cgl_bn2d_fwd(const float* X, int n, int hw, int C, int groups, const float* 
   f.run_mean = running_mean; f.run_var = running_var; f.save_mean = save_mean; f.save_invstd = save_invstd;
   f.coef0 = c0; f.coef1 = c1;
   f.nocache = fin_nocache();
-  hipLaunchKernelGGL(cgl_bn_finalize, dim3(C), dim3(256), 0, s, f);
+  CGL_LAUNCH(CGL_REC(CGL_K_BN_FINALIZE, f.mode, 0, f.nv ? CGL_LF_NVALID : 0), cgl_bn_finalize, dim3(C), dim3(256), 0, s,
+             f);
   CglEltArgs e;
   std::memset(&e, 0, sizeof(e));
   e.mode = 0; e.rows = (int)rows; e.C = C; e.gr = (int)gr; e.hw = hw; e.act = act; e.slope = slope;
   e.X = X; e.coef0 = c0; e.coef1 = c1; e.out = Y;
   const long n4 = rows * C / 4;
-  hipLaunchKernelGGL(cgl_eltwise, dim3((unsigned)std::min<long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, e);
+  CGL_LAUNCH(CGL_REC(CGL_K_ELTWISE, e.mode, 0, e.nv ? CGL_LF_NVALID : 0), cgl_eltwise,
+             dim3((unsigned)std::min<long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, e);
   return (int)hipGetLastError();
 }
 
@@ -4890,7 +5003,7 @@ int cgl_bn2d_fwd_stats(const double* part, int R, const float* X, int n, int hw,
                        const float* beta, double eps, double momentum, float* running_mean, float* running_var,
                        int act, float slope, float* Y, float* save_mean, float* save_invstd, void* scratch,
                        const int* nvalid, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   return cgl_bn2d_fwd_stats_coef(part, R, X, n, hw, C, groups, gamma, beta, eps, momentum, running_mean, running_var,
                                  act, slope, Y, save_mean, save_invstd, scratch, nullptr, 0, nvalid, ws, wsb, stream);
 }
@@ -4900,7 +5013,7 @@ int cgl_bn2d_fwd_stats_coef(const double* part, int R, const float* X, int n, in
                             float* running_var, int act, float slope, float* Y, float* save_mean, float* save_invstd,
                             void* scratch, float* coef, int apply_img0, const int* nvalid, void* ws, int64_t wsb,
                             void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   if (!part || !X || !Y || !gamma || !beta || !ws || !al16(ws) || !al16(X) || !al16(Y)) return CGL_E_ARG;
   if ((coef && !al16(coef)) || apply_img0 < 0 || apply_img0 > n) return CGL_E_ARG;
   if (n < 1 || hw < 1 || C % 4 != 0 || !pow2_le256(C) || groups < 1 || n % groups || (act != 0 && act != 1))
@@ -4934,10 +5047,12 @@ int cgl_bn2d_fwd_stats_coef(const double* part, int R, const float* X, int n, in
     if (a.S > CGL_FIN_MAXS) a.L = (cpg + CGL_FIN_MAXS - 1) / CGL_FIN_MAXS, a.S = (cpg + a.L - 1) / a.L;
     a.ctr = (unsigned int*)scratch;
     a.sl = (double*)((char*)scratch + al256((int64_t)C * 4));
-    hipLaunchKernelGGL(cgl_bn_finalize_sliced, dim3(a.S, C), dim3(256), 0, s, a);
+    CGL_LAUNCH(CGL_REC(CGL_K_BN_FINALIZE_SLICED, f.mode, 0, f.nv ? CGL_LF_NVALID : 0), cgl_bn_finalize_sliced,
+               dim3(a.S, C), dim3(256), 0, s, a);
   } else {
     f.nocache = fin_nocache();
-  hipLaunchKernelGGL(cgl_bn_finalize, dim3(C), dim3(256), 0, s, f);
+  CGL_LAUNCH(CGL_REC(CGL_K_BN_FINALIZE, f.mode, 0, f.nv ? CGL_LF_NVALID : 0), cgl_bn_finalize, dim3(C), dim3(256), 0, s,
+             f);
   }
   // apply to images [apply_img0, n) only (a consumer folds the rest into its operand load from `coef`)
   const int64_t row0 = (int64_t)apply_img0 * hw, arows = rows - row0;
@@ -4948,7 +5063,8 @@ int cgl_bn2d_fwd_stats_coef(const double* part, int R, const float* X, int n, in
   e.row0 = (int)row0;
   e.X = X + row0 * C; e.coef0 = c0; e.coef1 = c1; e.out = Y + row0 * C;
   const long n4 = arows * C / 4;
-  hipLaunchKernelGGL(cgl_eltwise, dim3((unsigned)std::min<long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, e);
+  CGL_LAUNCH(CGL_REC(CGL_K_ELTWISE, e.mode, 0, e.nv ? CGL_LF_NVALID : 0), cgl_eltwise,
+             dim3((unsigned)std::min<long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, e);
   return (int)hipGetLastError();
 }
 
@@ -4957,7 +5073,7 @@ int cgl_bn2d_bwd_stats(const double* part, int R, const float* dY, const float* 
                        float slope, const float* post_out, const float* drop, float* dX, float* dgamma, float* dbeta,
                        const float* post_coef, int post_coef_ld, const int* nvalid, double* colsum_part, void* ws,
                        int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   if (post_coef && (post || groups != 1 || !al16(post_coef) || post_coef_ld % 4)) return CGL_E_ARG;
   // C < 4 first: 256 % (C / 4) divides by zero for C = 0 (C = 1 .. 3 leave at C % 4)
   if (colsum_part && (((uintptr_t)colsum_part & 15) || C < 4 || C % 4 || 256 % (C / 4) || ((int64_t)n * hw) % 256))
@@ -4982,7 +5098,8 @@ int cgl_bn2d_bwd_stats(const double* part, int R, const float* dY, const float* 
   f.dgamma = dgamma; f.dbeta = dbeta;
   f.nv = nvalid; f.hw = hw;
   f.nocache = fin_nocache();
-  hipLaunchKernelGGL(cgl_bn_finalize, dim3(C), dim3(256), 0, s, f);
+  CGL_LAUNCH(CGL_REC(CGL_K_BN_FINALIZE, f.mode, 0, f.nv ? CGL_LF_NVALID : 0), cgl_bn_finalize, dim3(C), dim3(256), 0, s,
+             f);
   CglEltArgs e;
   std::memset(&e, 0, sizeof(e));
   e.mode = 1; e.rows = (int)rows; e.C = C; e.gr = (int)gr; e.hw = hw; e.slope = slope;
@@ -4991,10 +5108,12 @@ int cgl_bn2d_bwd_stats(const double* part, int R, const float* dY, const float* 
   e.psc = post_coef; e.psc_ld = post_coef_ld;
   const long n4 = rows * C / 4;
   if (colsum_part) {   // + the output's column sums per 256-row chunk (a bias gradient's col_sum partials)
-    hipLaunchKernelGGL(cgl_bnb_apply_colsum<CGL_BNB_NB>, dim3((unsigned)(rows / 256)), dim3(256), 0, s, e, colsum_part);
+    CGL_LAUNCH(CGL_REC(CGL_K_BNB_APPLY_COLSUM, e.mode, 0, e.nv ? CGL_LF_NVALID : 0), cgl_bnb_apply_colsum<CGL_BNB_NB>,
+               dim3((unsigned)(rows / 256)), dim3(256), 0, s, e, colsum_part);
     return (int)hipGetLastError();
   }
-  hipLaunchKernelGGL(cgl_eltwise, dim3((unsigned)std::min<long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, e);
+  CGL_LAUNCH(CGL_REC(CGL_K_ELTWISE, e.mode, 0, e.nv ? CGL_LF_NVALID : 0), cgl_eltwise,
+             dim3((unsigned)std::min<long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, e);
   return (int)hipGetLastError();
 }
 
@@ -5002,7 +5121,7 @@ int cgl_bn2d_bwd(const float* dY, const float* post, const float* X, int n, int 
                  const float* save_mean, const float* save_invstd, const float* gamma, float slope,
                  const float* post_out, const float* drop, float* dX, float* dgamma, float* dbeta,
                  const float* post_coef, int post_coef_ld, const int* nvalid, void* ws, int64_t wsb, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   if (post_coef && (post || groups != 1 || !al16(post_coef) || post_coef_ld % 4)) return CGL_E_ARG;
   if (!dY || !X || !save_mean || !save_invstd || !gamma || !dX || !ws || !al16(ws)) return CGL_E_ARG;
   if (!al16(dY) || !al16(X) || !al16(dX) || (post && !al16(post)) || (post_out && !al16(post_out))) return CGL_E_ARG;
@@ -5031,7 +5150,8 @@ int cgl_bn2d_bwd(const float* dY, const float* post, const float* X, int n, int 
   f.dgamma = dgamma; f.dbeta = dbeta;
   f.nv = nvalid; f.hw = hw;
   f.nocache = fin_nocache();
-  hipLaunchKernelGGL(cgl_bn_finalize, dim3(C), dim3(256), 0, s, f);
+  CGL_LAUNCH(CGL_REC(CGL_K_BN_FINALIZE, f.mode, 0, f.nv ? CGL_LF_NVALID : 0), cgl_bn_finalize, dim3(C), dim3(256), 0, s,
+             f);
   CglEltArgs e;
   std::memset(&e, 0, sizeof(e));
   e.mode = 1; e.rows = (int)rows; e.C = C; e.gr = (int)gr; e.hw = hw; e.slope = slope;
@@ -5039,13 +5159,14 @@ int cgl_bn2d_bwd(const float* dY, const float* post, const float* X, int n, int 
   e.gamma = gamma; e.post_out = post_out; e.drop = drop; e.out = dX; e.nv = nvalid;
   e.psc = post_coef; e.psc_ld = post_coef_ld;
   const long n4 = rows * C / 4;
-  hipLaunchKernelGGL(cgl_eltwise, dim3((unsigned)std::min<long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, e);
+  CGL_LAUNCH(CGL_REC(CGL_K_ELTWISE, e.mode, 0, e.nv ? CGL_LF_NVALID : 0), cgl_eltwise,
+             dim3((unsigned)std::min<long>((n4 + 255) / 256, 8192)), dim3(256), 0, s, e);
   return (int)hipGetLastError();
 }
 
 int cgl_act_drop_bwd(const float* dY, const float* post, const float* drop, int n, int hw, int C, float slope,
                      int tanh_y, float* dX, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   if (!dY || !dX || n < 1 || hw < 1 || C < 1) return CGL_E_ARG;
   if (tanh_y && !post) return CGL_E_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -5060,15 +5181,17 @@ int cgl_act_drop_bwd(const float* dY, const float* post, const float* drop, int 
   const long tot = (long)n * hw * C;
   const bool v4 = C % 4 == 0 && al16(dY) && al16(dX) && (!post || al16(post)) && (!drop || al16(drop));
   if (v4)
-    hipLaunchKernelGGL(cgl_eltwise, dim3((unsigned)std::min<long>((tot / 4 + 255) / 256, 8192)), dim3(256), 0, s, e);
+    CGL_LAUNCH(CGL_REC(CGL_K_ELTWISE, e.mode, 0, 0), cgl_eltwise,
+               dim3((unsigned)std::min<long>((tot / 4 + 255) / 256, 8192)), dim3(256), 0, s, e);
   else
-    hipLaunchKernelGGL(cgl_eltwise1, dim3((unsigned)std::min<long>((tot + 255) / 256, 8192)), dim3(256), 0, s, e);
+    CGL_LAUNCH(CGL_REC(CGL_K_ELTWISE1, e.mode, 0, 0), cgl_eltwise1,
+               dim3((unsigned)std::min<long>((tot + 255) / 256, 8192)), dim3(256), 0, s, e);
   return (int)hipGetLastError();
 }
 
 int cgl_act_drop_bwd_colsum(const float* dY, const float* post, const float* drop, int n, int hw, int C, float slope,
                             int tanh_y, float* dX, double* part, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   const long tot = (long)n * hw * C;
   if (!dY || !dX || !part || n < 1 || hw < 1 || C != 1 || tot > 8192L * 256 || ((uintptr_t)part & 15)) return CGL_E_ARG;
   if (tanh_y && !post) return CGL_E_ARG;
@@ -5081,19 +5204,23 @@ int cgl_act_drop_bwd_colsum(const float* dY, const float* post, const float* dro
   else e.post_out = post;
   e.drop = drop;
   e.colsum = part;
-  hipLaunchKernelGGL(cgl_eltwise1, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e);
+  CGL_LAUNCH(CGL_REC(CGL_K_ELTWISE1, e.mode, 0, 0), cgl_eltwise1, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
+             (hipStream_t)stream, e);
   return (int)hipGetLastError();
 }
 
 int cgl_colsum_finalize(const double* part, int nch, int C, float* out, void* stream) {
-  CGL_BATCH_GUARD();
+  CGL_CONV_ENTRY();
   if (!part || !out || nch < 1 || C < 1) return CGL_E_ARG;
   CglBnFinArgs f;
   std::memset(&f, 0, sizeof(f));
   f.part = part; f.C = C; f.groups = 1; f.chunks_per_group = nch; f.mode = 2; f.dgamma = out;
   f.nocache = fin_nocache();
-  if (t_wdefer.on && t_wdefer.add_fin(f)) return CGL_OK;   // rides in the deferred reductions' launch
-  hipLaunchKernelGGL(cgl_bn_finalize, dim3(C), dim3(256), 0, (hipStream_t)stream, f);
+  if (t_wdefer.on && t_wdefer.add_fin(f)) {   // rides in the deferred reductions' launch
+    cgl_conv_rec(CGL_K_BN_FINALIZE, f.mode, 0, CGL_LF_DEFERRED, dim3(C), dim3(256), 0);
+    return CGL_OK;
+  }
+  CGL_LAUNCH(CGL_REC(CGL_K_BN_FINALIZE, f.mode, 0, 0), cgl_bn_finalize, dim3(C), dim3(256), 0, (hipStream_t)stream, f);
   return (int)hipGetLastError();
 }
 

@@ -494,6 +494,48 @@ int cgl_conv_wgrad_defer_counters(int* counters, int n, int v, int* snap, int sn
 int cgl_conv_set_mma_dtype(int dtype);
 int cgl_conv_get_mma_dtype(void);
 
+/* ---- launch record (diagnostics) -------------------------------------------------------------
+ * What the host dispatch of the conv path launched, so that a test can assert the kernel a call reached instead
+ * of restating the selection code.  Host only and per thread: every launch site stores one record beside its
+ * launch (a few integers; nothing is read back from the device and no launch argument changes). */
+enum {                                 /* cgl_conv_launch_rec.kernel: one id per __global__ */
+  CGL_K_NONE = 0, CGL_K_CONV_PACK, CGL_K_CONV_FWD, CGL_K_CONV_FWD_HALO, CGL_K_CONV_N1, CGL_K_CONV_N1_PART,
+  CGL_K_CONV_N1_TILE, CGL_K_CONV_C1_FWD, CGL_K_CONV_BWD_N1, CGL_K_CONV_WGRAD, CGL_K_CONV_WGRAD_LDS,
+  CGL_K_CONV_WGRAD_N1, CGL_K_CONV_WGRAD_N1T, CGL_K_CONV_C1_WGRAD, CGL_K_CONV_C1_WGRAD_FIN, CGL_K_CONV_WGRAD_REDUCE,
+  CGL_K_DENSE1_WGRAD, CGL_K_CHAN_REDUCE, CGL_K_CHAN_REDUCE4, CGL_K_COLSUM, CGL_K_BN_FINALIZE,
+  CGL_K_BN_FINALIZE_SLICED, CGL_K_ELTWISE, CGL_K_ELTWISE1, CGL_K_BNB_APPLY_COLSUM, CGL_K_COUNT
+};
+enum {                                 /* cgl_conv_launch_rec.flags */
+  CGL_LF_FAST = 1 << 0,                /* template FAST (16-k chunks inside one tap) */
+  CGL_LF_BNIN = 1 << 1,                /* template BNIN (the input's BatchNorm folded into the operand load) */
+  CGL_LF_LDSM = 1 << 2,                /* template LDSM (LDS-staged operand panels of the 128 x 128 tiling) */
+  CGL_LF_HALO = 1 << 3,                /* the halo kernel of the upsampling conv */
+  CGL_LF_ROW = 1 << 4,                 /* template ROW of the wave-unit weight gradient */
+  CGL_LF_BF16 = 1 << 5,                /* bf16 MFMA operands */
+  CGL_LF_STATS_FWD = 1 << 6,           /* forward BatchNorm partials written by the launch */
+  CGL_LF_STATS_BWD = 1 << 7,           /* backward BatchNorm partials written by the launch */
+  CGL_LF_NVALID = 1 << 8,              /* a short first group (nvalid given) */
+  CGL_LF_BIAS_COL = 1 << 9,            /* weight gradient / reduction with the bias column */
+  CGL_LF_ILV = 1 << 10,                /* interleaved tile order of the launch's problems */
+  CGL_LF_STAGE = 1 << 11,              /* cgl_conv_wgrad_n1t with the LDS-staged dY window */
+  CGL_LF_DEFERRED = 1 << 12            /* recorded into an open batch / deferral instead of launched */
+};
+typedef struct cgl_conv_launch_rec {
+  int kernel;                 /* CGL_K_*: one id per __global__ the conv / dense / bn2d entry points launch */
+  int tm, tn, wm, wn, wk;     /* template / tiling parameters (0 where the kernel has none) */
+  int flags;                  /* CGL_LF_* bits */
+  int grid, block, lds_bytes; /* as launched (grid: workgroups, all dimensions multiplied) */
+  int np, splits;             /* problems of the launch; pixel splits of problem 0 (weight gradient) */
+} cgl_conv_launch_rec;
+#define CGL_CONV_LAUNCH_REC_MAX 8
+/* The launches of the calling thread's most recent cgl_conv3x3_* / cgl_dense_* / cgl_bn2d_* / cgl_act_drop_bwd* /
+ * cgl_colsum_finalize call, in order (pack, main kernel, reductions, column sums, finalize, apply): copies
+ * min(count, max) records, returns count (a call stores at most CGL_CONV_LAUNCH_REC_MAX and launches fewer).
+ * cgl_conv_wgrad_n1t records its pixels per lane and step as tm and its image width as tn; cgl_conv_n1_tile and
+ * cgl_conv_bwd_n1 their template constants as tm / tn; mode-dependent kernels (the channel reductions,
+ * cgl_bn_finalize, cgl_eltwise) their mode as tm. */
+int cgl_conv_last_launches(cgl_conv_launch_rec* out, int max);
+
 /* ---- device round log of the conv round ------------------------------------------------------
  * One completed conv round's scalars: what the reference prints after every communication round (F and Lambda,
  * capgan.py:177-183) plus the losses behind them.  The conv ops have no context object, so the ring --

@@ -39,6 +39,65 @@ def test_nm_exports():
         assert re.search(rf"\bT {name}$", out, re.M), name
 
 
+def _header_enum(prefix):
+    """The names of the header's enumerators with this prefix, in declaration order"""
+    src = open(os.path.join(ROOT, "include", "cglgan.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return re.findall(rf"\b({prefix}[A-Z0-9_]+)\b\s*(?:=[^,}}]*)?[,}}\n]", src)
+
+
+def test_launch_record_tables_match_header():
+    """cgl_conv_launch_rec and the CGL_K_* / CGL_LF_* tables of cglgan._lib follow include/cglgan.h: twelve ints, one
+    kernel name per id in enum order (CGL_K_COUNT of them), one flag name per bit."""
+    ks = _header_enum("CGL_K_")
+    assert ks[0] == "CGL_K_NONE" and ks[-1] == "CGL_K_COUNT"
+    assert len(C.CONV_KERNELS) == len(ks) - 1
+    for name, k in zip(C.CONV_KERNELS[1:], ks[1:-1]):      # CGL_K_CONV_FWD <-> cgl_conv_fwd, CGL_K_COLSUM <-> cgl_colsum_k
+        assert name in ("cgl_" + k[6:].lower(), "cgl_" + k[6:].lower() + "_k"), (name, k)
+    assert ["CGL_LF_" + f for f in C.CONV_LAUNCH_FLAGS] == _header_enum("CGL_LF_")
+    src = open(os.path.join(ROOT, "include", "cglgan.h")).read()
+    body = re.search(r"typedef struct cgl_conv_launch_rec \{(.*?)\} cgl_conv_launch_rec;", src, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = [f.strip() for decl in re.findall(r"int ([^;]*);", body) for f in decl.split(",")]
+    assert fields == [f for f, _ in C.ConvLaunchRec._fields_] and ctypes.sizeof(C.ConvLaunchRec) == 4 * len(fields)
+    assert int(re.search(r"#define CGL_CONV_LAUNCH_REC_MAX (\d+)", src).group(1)) == C.CONV_LAUNCH_REC_MAX
+
+
+def test_launch_record_refused_call_is_empty():
+    """A call refused on its arguments launched nothing: the record is empty (it is cleared on entry)."""
+    from cglgan import conv_ops as O
+    lib = C.lib
+    assert lib.cgl_conv3x3_fwd(None, None, None, None, 2, 6, 5, 12, 20, 1, 0, 0, 0.2, None, None, 0, None) == C_E_ARG
+    assert O.last_launches() == []
+    assert lib.cgl_conv_last_launches(None, 0) == 0
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="issues a launch with fabricated addresses: only where no "
+                                                      "device can take it (the GPU tests read the record of real calls)")
+def test_launch_record_host_side():
+    """The record is written where the launch is issued, so it can be read without a device: the dispatch of a
+    forward stores its main kernel with the launch's own grid, every entry clears it, and it is per thread.  Without
+    a device the launch itself is refused by the runtime; the record of what was issued stays."""
+    import threading
+    from cglgan import conv_ops as O
+    lib = C.lib
+    fake, ws = ctypes.c_void_p(1 << 24), 1 << 40              # never dereferenced on the host
+    assert lib.cgl_conv3x3_fwd_packed(fake, fake, fake, fake, 33, 31, 32, 16, 192, 1, 0, 0, 0.2, None, fake, ws, None) != 0
+    ls = O.last_launches()
+    assert [l.kernel for l in ls] == ["cgl_conv_fwd"]
+    l = ls[0]
+    assert (l.tm, l.tn, l.wm, l.wn, l.wk) == (2, 2, 2, 2, 1) and l.flags == {"FAST", "LDSM"}
+    assert l.grid == 256 * 2 and l.block == 256 and l.lds_bytes == 2 * 2 * 128 * 20 * 4 and l.np == 1
+    seen = []
+    t = threading.Thread(target=lambda: seen.append(O.last_launches()))
+    t.start()
+    t.join()
+    assert seen == [[]] and len(O.last_launches()) == 1       # another thread's record is its own
+    assert lib.cgl_bn2d_fwd(None, 1, 1, 4, 1, None, None, 0.8, 0.1, None, None, 1, 0, 0.2, None, None, None, None, None,
+                            0, None) == C_E_ARG
+    assert O.last_launches() == []                            # cleared on entry
+
+
 def _cfg(g, d, B=64, Br=None, loss=C.LOSS_CE2, epoch=1, n_workers=1, rank=0, xl=-1):
     cfg = C.GanConfig()
     cfg.g, cfg.d = _spec(g), _spec(d)
