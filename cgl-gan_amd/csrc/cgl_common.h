@@ -1,6 +1,6 @@
 // Device / host helpers shared by the two translation units of libcglgan_hip (the MLP step:
 // cgl_runtime.hip with cgl_gemm.hip + cgl_kernels.hip; the conv path: cgl_conv_tu.hip with
-// cgl_conv.hip + cgl_eval.hip).  Included by cgl_internal.h.
+// cgl_conv.hip + cgl_eval.hip, and cgl_conv_bf16.hip, which share cgl_conv_mma.h).  Included by cgl_internal.h.
 #pragma once
 
 // Launch batching (cgl_conv_batch_begin / _end, cgl_conv.hip): while the calling thread has a batch open,

@@ -1,7 +1,8 @@
 // Second translation unit of libcglgan_hip: the conv GAN path of model/lsgan.py (implicit-GEMM
 // convolutions, BatchNorm2d, losses, Adam) and the evaluation kernels.  Compiled separately from
 // the MLP step (cgl_runtime.hip) so that either side rebuilds alone; shared helpers live in
-// cgl_common.h.
+// cgl_common.h.  cgl_conv.hip takes the MFMA kernels from cgl_conv_mma.h and instantiates them for
+// fp32 here; cgl_conv_bf16.hip holds their bf16 instances.
 #include "cgl_internal.h"
 
 #include <algorithm>
