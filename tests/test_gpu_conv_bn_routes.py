@@ -1,4 +1,4 @@
-"""BatchNorm2d of the conv path (cgl_bn2d_* in csrc/cgl_conv.hip) at the shapes and forms no other test reaches,
+"""BatchNorm2d of the conv path (cgl_bn2d_* in csrc/cgl_conv_bn.hip) at the shapes and forms no other test reaches,
 against fp64 F.batch_norm + autograd, with elementwise bounds in the form DESIGN.md 5a derived for BatchNorm1d.
 
 What the cases are for (the launch record, conv_ops.last_launches, names the kernel that ran):
@@ -11,7 +11,9 @@ What the cases are for (the launch record, conv_ops.last_launches, names the ker
     sum of C 1 or 2), in every mode.  Its rows are split over 256 / C lanes per channel where cgl_chan_reduce4 uses
     1024 / C, so the two sum in different orders: each is held to the reference, and on integer data (every sum
     exact) they must agree to the bit;
-  * cgl_colsum_k (column sums at a channel count that is no power of two) with a ragged last 32-row chunk.
+  * cgl_colsum_k (column sums at a channel count that is no power of two) with a ragged last 32-row chunk;
+  * the two entry points of a direction are one path: cgl_bn2d_fwd / cgl_bn2d_bwd leave their chunk partials in the
+    workspace, and the _stats form given those partials must write the same bits from the same launches.
 
 Bounds, u = 2^-24, sc = invstd gamma (the reductions accumulate in double, so only the fp32 roundings of the
 finalize and the apply count):
@@ -342,6 +344,104 @@ def test_bn2d_nvalid(hw, ng, C, groups, nvk, scalar):
         ratio(dg, dgr, dgb, tag + " dgamma", rat)
         ratio(db, dbr, dbb, tag + " dbeta", rat)
     finish(rat)
+
+
+def chan_chunk(gr):
+    """chan_chunk's default rule (csrc/cgl_conv_bn.h, CGL_CHAN_MINCH unset): the rows per chunk of cgl_bn2d_fwd's and
+    cgl_bn2d_bwd's own reduction"""
+    R = 128
+    while R > 1 and gr % R:
+        R //= 2
+    while R > 32 and gr // R < 64 and gr % (R // 2) == 0:
+        R //= 2
+    return R
+
+
+def own_partials(n, hw, C, groups, R):
+    """The chunk partials [n hw / R][C][2] (double) that cgl_bn2d_fwd / cgl_bn2d_bwd left at the start of the
+    stream's workspace, cloned: the next call carves its coefficients out of the same buffer."""
+    O = ops()
+    ws = O.workspace(O.bn2d_ws_bytes(n, hw, C, groups), DEV)
+    return ws[:n * hw // R * C * 16].view(torch.float64).clone()
+
+
+# (hw, images per call, C, groups, nvalid): 147 rows per call (odd: chunks of one row), 64 rows per call in two
+# chunks of 32, and the latter as a short first call
+ONE_PATH = [(49, 3, 8, 2, None), (16, 4, 64, 2, None), (16, 4, 64, 2, 1)]
+
+
+def _one_path_setup(hw, ng, groups):
+    if "CGL_CHAN_MINCH" in os.environ:
+        pytest.skip("chan_chunk is restated here for the default CGL_CHAN_MINCH")
+    return ops(), ng * groups, chan_chunk(ng * hw)
+
+
+@pytest.mark.parametrize("act", [0, 1])
+@pytest.mark.parametrize("hw,ng,C,groups,nv", ONE_PATH)
+def test_bn2d_fwd_entry_points_are_one_path(hw, ng, C, groups, nv, act):
+    """cgl_bn2d_fwd is its own channel reduction followed by what cgl_bn2d_fwd_stats does: given the partials the
+    first left in the workspace and its chunk size, the second must write the same bits (y, saved and running
+    statistics) from the same launches less the reduction -- the unsliced finalize, as no scratch is given."""
+    O, n, R = _one_path_setup(hw, ng, groups)
+    d = make(n, hw, C, seed=11 * hw + ng + C + groups + act)
+    y, rm, rv, sm, si, ls = run_fwd(d, n, hw, C, groups, act, nv=nv)
+    part = own_partials(n, hw, C, groups, R)
+    assert [l.kernel for l in ls] == ["cgl_chan_reduce4", "cgl_bn_finalize", "cgl_eltwise"]
+    assert ls[0].grid == n * hw // R, "rows per reduction chunk"
+    y2, y2buf = padded(n * hw * C)
+    y2.fill_(float("nan"))
+    rm2, rv2 = d["rm"].to(DEV), d["rv"].to(DEV)
+    sm2, si2 = torch.empty(groups, C, device=DEV), torch.empty(groups, C, device=DEV)
+    nvd = torch.tensor([nv], dtype=torch.int32, device=DEV) if nv is not None else None
+    O.bn2d_fwd_stats(part, d["x"].to(DEV), n, hw, C, d["gamma"].to(DEV), d["beta"].to(DEV), y2, groups=groups, eps=EPS,
+                     momentum=MOM, running_mean=rm2, running_var=rv2, act=act, slope=SLOPE, save_mean=sm2,
+                     save_invstd=si2, R=R, nvalid=nvd)
+    assert O.last_launches() == ls[1:], "the record of cgl_bn2d_fwd less its reduction"
+    torch.cuda.synchronize()
+    canary_ok(y2buf, y2.numel(), "y (stats)")
+    assert not torch.isnan(y).any(), "NaN left in y"
+    for a, b, k in ((y, y2.view(n, hw, C), "y"), (sm, sm2, "save_mean"), (si, si2, "save_invstd"),
+                    (rm, rm2, "running_mean"), (rv, rv2, "running_var")):
+        assert torch.equal(a, b), f"{k}: cgl_bn2d_fwd and cgl_bn2d_fwd_stats differ"
+
+
+@pytest.mark.parametrize("hw,ng,C,groups,nv,how", [s + ("post",) for s in ONE_PATH] + [(16, 8, 64, 1, None, "post_coef")])
+def test_bn2d_bwd_entry_points_are_one_path(hw, ng, C, groups, nv, how):
+    """cgl_bn2d_bwd against cgl_bn2d_bwd_stats on the partials it left: dX, dgamma and dbeta to the bit, and the
+    same launches less the reduction.  LeakyReLU' from post, and once from post_coef (one call: groups = 1)."""
+    O, n, R = _one_path_setup(hw, ng, groups)
+    d = make(n, hw, C, seed=13 * hw + ng + C + groups)
+    if nv is not None:
+        d["dy"][nv:ng] = 0            # padding images carry no loss (test_bn2d_nvalid)
+    y, _, _, sm, si, _ = run_fwd(d, n, hw, C, groups, 1, nv=nv)
+    if how == "post":
+        kw = dict(post=y.contiguous())
+    else:
+        g = torch.Generator().manual_seed(5)
+        coef = torch.stack([torch.randn(C, generator=g), 0.3 * torch.randn(C, generator=g)]).float().contiguous()
+        kw = dict(post_coef=(coef.to(DEV), 0, 1))
+    nvd = torch.tensor([nv], dtype=torch.int32, device=DEV) if nv is not None else None
+    kw.update(groups=groups, slope=SLOPE, nvalid=nvd)
+    res, part, ls1 = [], None, None
+    for stats in (False, True):
+        dx, dxbuf = padded(n * hw * C)
+        dx.fill_(float("nan"))
+        dg, db = torch.empty(C, device=DEV), torch.empty(C, device=DEV)
+        args = (d["dy"].to(DEV), d["x"].to(DEV), n, hw, C, sm.contiguous(), si.contiguous(), d["gamma"].to(DEV), dx)
+        if stats:
+            O.bn2d_bwd_stats(part, *args, R=R, dgamma=dg, dbeta=db, **kw)
+            assert O.last_launches() == ls1[1:], "the record of cgl_bn2d_bwd less its reduction"
+        else:
+            O.bn2d_bwd(*args, dgamma=dg, dbeta=db, **kw)
+            ls1 = O.last_launches()
+            part = own_partials(n, hw, C, groups, R)
+            assert [l.kernel for l in ls1] == ["cgl_chan_reduce4", "cgl_bn_finalize", "cgl_eltwise"]
+            assert ls1[0].grid == n * hw // R, "rows per reduction chunk"
+        torch.cuda.synchronize()
+        canary_ok(dxbuf, dx.numel(), "dx")
+        res.append((dx, dg, db))
+    for a, b, k in zip(res[0], res[1], ("dX", "dgamma", "dbeta")):
+        assert not torch.isnan(a).any() and torch.equal(a, b), f"{k}: cgl_bn2d_bwd and cgl_bn2d_bwd_stats differ"
 
 
 @pytest.mark.parametrize("ints", [False, True], ids=["normal", "integers"])
