@@ -44,9 +44,15 @@ EXPORTS = [
     "cgl_bn2d_fwd_stats", "cgl_bn2d_fwd_stats_coef", "cgl_conv3x3_fwd_packed_bnin", "cgl_bn2d_stats_scratch_bytes", "cgl_linear_desc_bytes", "cgl_linear_prepare", "cgl_linear_prepare_gather", "cgl_linear_prepare_wgrad_nhwc",
     "cgl_linear_launch", "cgl_conv3x3_bwd_stat_chunks", "cgl_conv3x3_bwd_data_packed_stats", "cgl_conv3x3_bwd_data_stats", "cgl_bn2d_bwd_stats",
     "cgl_normal_fill_dev", "cgl_dropout2d_masks_dev", "cgl_adam_multi_dev", "cgl_sample_rows_dev", "cgl_counters_add",
+    # co-located conv workers (ConvGanStep(colocated=W)): grouped state ops, the exchange, the grouped round log
+    "cgl_sample_rows_dev_multi_desc_bytes", "cgl_sample_rows_dev_multi_prepare", "cgl_sample_rows_dev_multi",
+    "cgl_dropout2d_masks_dev_multi_desc_bytes", "cgl_dropout2d_masks_dev_multi_prepare",
+    "cgl_dropout2d_masks_dev_multi", "cgl_bcast_rows", "cgl_conv_alpha_combine", "cgl_conv_wgrad_defer_log_group",
+    "cgl_conv_round_log_group", "cgl_conv_batch_cancel",
     # evaluation (CGLGAN/2DMG/main.py plot_2d KL score)
     "cgl_kl_score",
 ]
+MASKS_MULTI_MAX = 128   # CGL_MASKS_MULTI_MAX
 
 LOSS_OP_CE2, LOSS_OP_BCE, LOSS_OP_MSE, LOSS_OP_BCE_LOGIT = 0, 1, 2, 3
 
@@ -118,6 +124,18 @@ class ConvRoundLogArgs(ctypes.Structure):
                 ("counters", ctypes.c_void_p), ("n_workers", ctypes.c_int), ("rank", ctypes.c_int),
                 ("weighting", ctypes.c_int), ("half", ctypes.c_float), ("round", ctypes.c_int),
                 ("g_step", ctypes.c_int), ("d_step", ctypes.c_int)]
+
+
+class SampleJob(ctypes.Structure):
+    """cgl_sample_job: one cgl_sample_rows_dev call of a cgl_sample_rows_dev_multi group."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("nv_out", ctypes.c_void_p),
+                ("seed", ctypes.c_ulonglong), ("n_src", ctypes.c_int), ("reserved_", ctypes.c_int)]
+
+
+class MaskJob(ctypes.Structure):
+    """cgl_mask_job: one mask of cgl_dropout2d_masks_dev_multi (a seed per mask)."""
+    _fields_ = [("mask", ctypes.c_void_p), ("n", ctypes.c_int), ("C", ctypes.c_int), ("seed", ctypes.c_ulonglong),
+                ("counter", ctypes.c_ulonglong)]
 
 
 class ConvLaunchRec(ctypes.Structure):
@@ -235,6 +253,7 @@ def _load():
         "cgl_conv_pack_multi": (ci, [ci, P(ConvPackJob), vp]),
         "cgl_conv_batch_begin": (ci, [vp]),
         "cgl_conv_batch_end": (ci, [vp]),
+        "cgl_conv_batch_cancel": (ci, []),
         "cgl_conv3x3_bias_by_colsum": (ci, [ci, ci, ci, ci, ci, ci, ci]),
         "cgl_conv_set_mma_dtype": (ci, [ci]),
         "cgl_conv_get_mma_dtype": (ci, []),
@@ -280,6 +299,16 @@ def _load():
                                          ctypes.c_ulonglong, vp]),
         "cgl_sample_rows_dev": (ci, [vp, ci, ci, ci, ctypes.c_ulonglong, vp, vp, vp, vp]),
         "cgl_counters_add": (ci, [vp, ci, ci, vp]),
+        "cgl_sample_rows_dev_multi_desc_bytes": (i64, [ci]),
+        "cgl_sample_rows_dev_multi_prepare": (ci, [ci, P(SampleJob), ci, ci, vp, P(ci)]),
+        "cgl_sample_rows_dev_multi": (ci, [vp, ci, vp, vp]),
+        "cgl_dropout2d_masks_dev_multi_desc_bytes": (i64, [ci]),
+        "cgl_dropout2d_masks_dev_multi_prepare": (ci, [ci, P(MaskJob), cd, vp, P(ci)]),
+        "cgl_dropout2d_masks_dev_multi": (ci, [vp, ci, ci, vp, ctypes.c_ulonglong, vp]),
+        "cgl_bcast_rows": (ci, [vp, i64, vp, i64, ci, vp]),
+        "cgl_conv_alpha_combine": (ci, [ci, ci, P(cf), vp, ci, vp, vp, i64, vp, vp, vp, vp]),
+        "cgl_conv_wgrad_defer_log_group": (ci, [P(ConvRoundLogArgs), ci]),
+        "cgl_conv_round_log_group": (ci, [P(ConvRoundLogArgs), ci, vp]),
         "cgl_version": (ctypes.c_char_p, []),
     }
     for name, (res, args) in sig.items():

@@ -13,7 +13,8 @@ from .driver import plan_chunks
 
 
 def train_conv(target, rounds, rounds_per_launch=10, log_every=0, log=print, start_round=None):
-    """``rounds`` rounds of ``target`` -- a ConvGanStep (N = 1) or a ConvWorkerExchange -- in launches of up to
+    """``rounds`` rounds of ``target`` -- a ConvGanStep (N = 1, or co-located: its lines carry worker 0's losses and
+    the server's F / lambda), a ConvWorkerExchange or a ConvColocatedExchange -- in launches of up to
     ``rounds_per_launch`` rounds (``run_rounds`` / ``exchange.rounds``: one hipGraph each on a one-worker graph
     step), cut by ``driver.plan_chunks`` and capped by the round log's capacity so that a whole launch is still in
     the ring when it is read.  With ``log_every`` a JSON line per due round with Driver.run's keys (``round,

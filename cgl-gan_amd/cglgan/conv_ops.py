@@ -398,7 +398,8 @@ class PackSet:
             raise RuntimeError(f"PackSet: bad geometry for {key} (rc={n})")
         self._jobs.append((group, key, w, int(n), (h, wd, cin, cout, stride, up, ks, dir)))
 
-    def finalize(self, device):
+    def finalize(self, device, unions=None):
+        """``unions``: {name: [groups]} -- further launch sets, each the jobs of several groups (``run(name)``)."""
         tot = sum((n + 63) // 64 * 64 for _, _, _, n, _ in self._jobs)
         self.buf = torch.zeros(max(tot, 64), dtype=torch.float32, device=device)
         recs, off = [], 0
@@ -410,6 +411,9 @@ class PackSet:
         for g in [None] + sorted({r[0] for r in recs}):
             sel = [j for grp, j in recs if g is None or grp == g]
             self._arrs[g] = (len(sel), (C.ConvPackJob * len(sel))(*sel))
+        for name, groups in (unions or {}).items():
+            sel = [j for grp, j in recs if grp in groups]
+            self._arrs[name] = (len(sel), (C.ConvPackJob * len(sel))(*sel))
         return self
 
     def __getitem__(self, key):
@@ -627,6 +631,105 @@ def round_log(args, **host):
         C.check(C.lib.cgl_conv_wgrad_defer_log(ctypes.byref(args)), "cgl_conv_wgrad_defer_log")
     else:
         C.check(C.lib.cgl_conv_round_log(ctypes.byref(args), _s()), "cgl_conv_round_log")
+
+
+def round_log_group(args, workers, **host):
+    """``round_log`` for a co-located step: ``workers`` records per round, one ring per worker (``args``: ring
+    [workers][capacity * 16], lbuf [workers][8], nv [workers], n_workers == workers, rank 0) -- in the deferred launch
+    inside wgrad_defer (cgl_conv_wgrad_defer_log_group), otherwise one launch (cgl_conv_round_log_group)."""
+    for k, v in host.items():
+        setattr(args, k, int(v))
+    if _WDEFER:
+        C.check(C.lib.cgl_conv_wgrad_defer_log_group(ctypes.byref(args), int(workers)),
+                "cgl_conv_wgrad_defer_log_group")
+    else:
+        C.check(C.lib.cgl_conv_round_log_group(ctypes.byref(args), int(workers), _s()), "cgl_conv_round_log_group")
+
+
+class SampleRowsMulti:
+    """W sample_rows_dev calls over one ``round_dev`` as one launch (cgl_sample_rows_dev_multi): ``jobs`` =
+    [(src, seed, dst, nv_out or None)], every ``dst`` [nrows, f].  The job table is written to device memory here,
+    once (a synchronous copy); ``__call__`` launches it, stream-ordered, capturable, batchable (launch_batch)."""
+
+    def __init__(self, jobs, nrows, round_dev):
+        n = len(jobs)
+        arr = (C.SampleJob * n)()
+        for a, (src, seed, dst, nv) in zip(arr, jobs):
+            _chk(src, dst)
+            if nv is not None and not (nv.is_cuda and nv.dtype == torch.int32):
+                raise ValueError("SampleRowsMulti: nv_out must be an int32 device tensor")
+            if src.dim() != 2 or not src.is_contiguous() or dst.numel() < nrows * src.shape[1]:
+                raise ValueError("SampleRowsMulti: src [n, f] contiguous, dst of nrows * f floats")
+            a.src, a.dst, a.nv_out = src.data_ptr(), dst.data_ptr(), nv.data_ptr() if nv is not None else None
+            a.seed, a.n_src = int(seed) & (2 ** 64 - 1), src.shape[0]
+        f = {src.shape[1] for src, _, _, _ in jobs}
+        if len(f) != 1:
+            raise ValueError("SampleRowsMulti: one row length for all jobs")
+        nb = C.lib.cgl_sample_rows_dev_multi_desc_bytes(n)
+        if nb < 0:
+            raise ValueError(f"SampleRowsMulti: {n} jobs (1 .. {C.MAX_COLOCATED})")
+        self._keep, self.n, self.nrows, self.round_dev = jobs, n, int(nrows), round_dev
+        self.desc = torch.zeros(int(nb), dtype=torch.uint8, device=round_dev.device)
+        blocks = ctypes.c_int(0)
+        C.check(C.lib.cgl_sample_rows_dev_multi_prepare(n, arr, self.nrows, f.pop(), _p(self.desc),
+                                                        ctypes.byref(blocks)), "cgl_sample_rows_dev_multi_prepare")
+        self.blocks = blocks.value
+
+    def __call__(self):
+        C.check(C.lib.cgl_sample_rows_dev_multi(_p(self.desc), self.blocks, _p(self.round_dev), _s()),
+                "cgl_sample_rows_dev_multi")
+
+
+class DropoutMasksMulti:
+    """dropout2d_masks_dev with a seed per mask, up to 128 masks in one launch (cgl_dropout2d_masks_dev_multi):
+    ``jobs`` = [(mask, n, c, seed, counter)]; counter j = counter + round_stride * round_dev[0].  Prepared once
+    (table in device memory), launched stream-ordered, capturable, batchable."""
+
+    def __init__(self, jobs, p, round_dev, round_stride):
+        n = len(jobs)
+        arr = (C.MaskJob * n)()
+        for a, (mask, nn, c, seed, ctr) in zip(arr, jobs):
+            _chk(mask)
+            if mask.numel() < nn * c:
+                raise ValueError("DropoutMasksMulti: mask smaller than n * c")
+            a.mask, a.n, a.C = mask.data_ptr(), int(nn), int(c)
+            a.seed, a.counter = int(seed) & (2 ** 64 - 1), int(ctr) & (2 ** 64 - 1)
+        nb = C.lib.cgl_dropout2d_masks_dev_multi_desc_bytes(n)
+        if nb < 0:
+            raise ValueError(f"DropoutMasksMulti: {n} masks (1 .. {C.MASKS_MULTI_MAX})")
+        self._keep, self.n, self.round_dev, self.round_stride = jobs, n, round_dev, int(round_stride)
+        self.desc = torch.zeros(int(nb), dtype=torch.uint8, device=round_dev.device)
+        blocks = ctypes.c_int(0)
+        C.check(C.lib.cgl_dropout2d_masks_dev_multi_prepare(n, arr, float(p), _p(self.desc), ctypes.byref(blocks)),
+                "cgl_dropout2d_masks_dev_multi_prepare")
+        self.blocks = blocks.value
+
+    def __call__(self):
+        C.check(C.lib.cgl_dropout2d_masks_dev_multi(_p(self.desc), self.n, self.blocks, _p(self.round_dev),
+                                                    self.round_stride, _s()), "cgl_dropout2d_masks_dev_multi")
+
+
+def bcast_rows(src, dst0, dst_stride, copies):
+    """dst0[q * dst_stride + i] = src[i], q < copies (floats; cgl_bcast_rows)."""
+    _chk(src, dst0)
+    C.check(C.lib.cgl_bcast_rows(_p(src), src.numel(), _p(dst0), int(dst_stride), int(copies), _s()),
+            "cgl_bcast_rows")
+
+
+def alpha_combine(weighting, beta, gloss, gloss_stride, lam_dev, d, dimg, alpha_all, losses_all):
+    """The co-located exchange (cgl_conv_alpha_combine): alpha from the W = d.shape[0] G losses gloss[q *
+    gloss_stride] and the device lambda, alpha_all / losses_all written, dimg = sum_q alpha_q d[q] in worker order
+    (bitwise W weights_scale calls and the ordered sum)."""
+    _chk(gloss, lam_dev, d, dimg, alpha_all, losses_all)
+    W = d.shape[0]
+    if len(beta) != W or not d.is_contiguous() or dimg.numel() != d[0].numel():
+        raise ValueError("alpha_combine: d [W, nx] contiguous, one beta per worker, dimg of nx floats")
+    if alpha_all.numel() < W or losses_all.numel() < W or gloss.numel() < (W - 1) * gloss_stride + 1:
+        raise ValueError("alpha_combine: alpha_all / losses_all / gloss too small for the workers")
+    arr = (ctypes.c_float * W)(*[float(b) for b in beta])
+    C.check(C.lib.cgl_conv_alpha_combine(WEIGHTING[weighting], W, arr, _p(gloss), int(gloss_stride), _p(lam_dev),
+                                         _p(d), d[0].numel(), _p(dimg), _p(alpha_all), _p(losses_all), _s()),
+            "cgl_conv_alpha_combine")
 
 
 def counters_add(counters, v=1):

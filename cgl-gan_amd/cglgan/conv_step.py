@@ -19,9 +19,16 @@ Data layout (HBM, all NHWC fp32):
 Parameters: one flat buffer per model (+ grads, Adam m, v), 256-byte aligned tensors in
 state-dict order, exposed as views under the reference's keys (``l1.0.weight``,
 ``conv_blocks.2.running_var``, ``model.14.bias``, ``adv_layer.weight`` ...).
+
+``ConvGanStep(colocated=W)`` runs a server's whole W-worker round (capgan.py:211-262 + :316-349) in this one
+context: z, G forward, G backward, the lambda step and G Adam once; per worker q its own D (``Ds[q]``), shard,
+sampler (seed + 1 + q), Dropout2d stream (seed * 7919 + q), D step, D Adam and G-loss pass; the alpha weighting and
+the sum of the W image gradients in one launch (cgl_conv_alpha_combine); W round-log records per round.  Bitwise
+the W lockstep contexts under cglgan.exchange.ConvLocalComm.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -143,11 +150,35 @@ def default_init(fm: FlatModel, generator=None):
 class ConvGanStep:
     """Fused CAPGAN worker round of the model/lsgan.py GAN (see module docstring)."""
 
-    def __init__(self, batch, loss="mse", data=None, seed=20211212, n_workers=1, rank=0, weighting="capgan",
+    def __init__(self, batch, loss="mse", data=None, seed=20211212, n_workers=None, rank=0, weighting="capgan",
                  lr=2e-4, betas=(0.5, 0.999), adam_eps=1e-8, gen_z=True, beta=None, device="cuda", graph=False,
-                 gemm_dtype="f32"):
+                 gemm_dtype="f32", colocated=None):
         if loss not in ("mse", "bce"):
             raise ValueError("loss must be 'mse' (LSGAN) or 'bce' (Sigmoid + BCELoss)")
+        # colocated=W (2 .. CGL_MAX_COLOCATED): this one context runs the server's whole W-worker round -- one G, W
+        # discriminators, the exchange inside the round (see the "co-located workers" section below).  The step itself
+        # is worker 0: everything up to that section allocates what the one-worker step allocates, in its order
+        W = self.colocated = int(colocated or 0)
+        shards = None
+        if colocated is not None and W != 0:
+            if not 2 <= W <= C.MAX_COLOCATED:
+                raise ValueError(f"colocated must be 2 .. {C.MAX_COLOCATED} workers (1 worker: leave it unset)")
+            if n_workers not in (None, W):
+                raise ValueError(f"colocated={W}: n_workers, when given, must be {W}")
+            if rank != 0:
+                raise ValueError("a co-located step holds every worker: rank must be 0")
+            if weighting not in O.WEIGHTING:
+                raise ValueError(f"weighting must be one of {sorted(O.WEIGHTING)}")
+            if data is not None:
+                if not isinstance(data, (list, tuple)) or len(data) != W or not all(
+                        torch.is_tensor(t) and t.dim() == 2 and t.shape[1] == 1024 and t.shape[0] >= 1 and t.is_cuda and
+                        t.dtype == torch.float32 for t in data):
+                    raise ValueError(f"colocated={W}: data must be a list of {W} [n >= 1, 1024] float32 GPU tensors "
+                                     "(one shard per worker)")
+                shards = [t.contiguous() for t in data]
+                data = shards[0]
+            n_workers = W
+        n_workers = 1 if n_workers is None else n_workers
         # operand type of the MFMA convolution kernels (conv_ops.mma_dtype; accumulation stays fp32; the
         # Conv2d(64, 1) / Conv2d(1, 16) vector kernels and both Linears stay fp32).  A constructor argument, not
         # state: resume_state() does not carry it
@@ -172,6 +203,7 @@ class ConvGanStep:
         self.y1, self.a1 = e(B2, 16, 16, 128), e(B2, 16, 16, 128)
         self.y2, self.a2 = e(B2, 32, 32, 64), e(B2, 32, 32, 64)
         self.x3 = e(3 * B, 32, 32, 1)
+        self.xin = self.x3     # the D step's input [real; Xd] (a co-located worker q > 0 has a [2B] tensor of its own)
         self.g_save = {k: (e(2, c), e(2, c)) for k, c in (("conv_blocks.2", 128), ("conv_blocks.6", 64))}
         # D activations (2B rows: D step; first B rows reused by the G-loss pass)
         self.q = [e(B2, hw // 2, hw // 2, co) for _, _, _, co, hw in D_CONVS]
@@ -235,7 +267,22 @@ class ConvGanStep:
         for ck, _, ci, co, hw in D_CONVS:
             pk.add("D", ck + "f", PD[ck + ".weight"], hw, hw, ci, co, 2, 0)
             pk.add("D", ck + "b", PD[ck + ".weight"], hw, hw, ci, co, 2, 0, dir=1)
-        self.pk = pk.finalize(dev)
+        # co-located: the other workers' discriminators join the pack set (group "D<q>", keys "<q>:<key>"); the round
+        # start packs G and every D in as few launches as cgl_conv_pack_multi's 48 problems allow (G + D0 = 32, then
+        # two discriminators = 40 per launch), the first of them inside the batched round start
+        self.Ds = [self.D] + [FlatModel(LSGAN_D, dev) for _ in range(1, W)]
+        self._pack_chunks = [None]
+        if W:
+            for q in range(1, W):
+                Pq = self.Ds[q].params
+                for ck, _, ci, co, hw in D_CONVS:
+                    pk.add(f"D{q}", f"{q}:{ck}f", Pq[ck + ".weight"], hw, hw, ci, co, 2, 0)
+                    pk.add(f"D{q}", f"{q}:{ck}b", Pq[ck + ".weight"], hw, hw, ci, co, 2, 0, dir=1)
+            unions = {"c0": ["G", "D"]}
+            for i, q in enumerate(range(1, W, 2)):
+                unions[f"c{i + 1}"] = [f"D{q}", f"D{q + 1}"]
+            self._pack_chunks = list(unions)
+        self.pk = pk.finalize(dev, **({"unions": unions} if W else {}))
         # G's nn.Linear(100, 8192) (model/lsgan.py:8) on the fused-MLP GEMM kernel, prepared once:
         # forward on [z1; z2] and its weight + bias gradient on the z2 rows
         GG = self.G.grads
@@ -375,6 +422,96 @@ class ConvGanStep:
                                           losses_all=self.losses_all if multi else None,
                                           alpha_all=self.alpha_all if multi else None,
                                           counters=self.dstate if graph else None)
+        self.workers = None
+        if W:
+            self._init_colocated(shards)
+
+    # ------------------------------------------------------------------ co-located workers
+    # The D side of the round -- D's FlatModel and packs, the D step's input, activations, masks, gradients, statistics
+    # partials and scratch, the head scratch, the weight-gradient workspaces, the loss words, the real-row count, the
+    # sampler and the round-log ring -- is one set of attributes per worker (WORKER_ATTRS).  The step's own attributes
+    # are worker 0's; ``_as_worker(q)`` makes worker q's the step's for a block, so that _d_forward / _head /
+    # _d_backward, the sampler and the masks run unchanged on that worker's buffers.
+    WORKER_ATTRS = ("D", "pk", "xin", "q", "r", "flat", "v", "d_save", "mask_d", "mask_g", "dv", "dr", "dc", "dq1",
+                    "dimg", "lbuf", "hscr_d", "hscr_g", "dcoef", "wws", "st_part", "st_scratch", "nv", "rlog", "rank",
+                    "data", "short", "_short_call", "_perm", "_pos", "_gen", "_nv_stale", "_head_coef", "_d_folded")
+
+    def _init_colocated(self, shards):
+        W, B, B2, dev = self.colocated, self.B, 2 * self.B, self.device
+        e = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        cap = self.log_capacity
+        # per-worker words laid out [W][...]: what the exchange launch and the grouped round log read
+        self.lbuf_all = e(W, 8)
+        self.nv_all = torch.full((W,), B, dtype=torch.int32, device=dev)
+        self.dimg_all = e(W, B, 32, 32, 1)          # worker q's d l_q / d Xg; self.dimg: their alpha-weighted sum
+        self.rlog_all = torch.zeros(W, 16 * cap, dtype=torch.int32, device=dev)
+        self.xin_rest = e(W - 1, B2, 32, 32, 1)     # [real_q; Xd] of the workers q > 0 (worker 0: x3[:2B])
+        self.lbuf, self.nv, self.rlog = self.lbuf_all[0], self.nv_all[0:1], self.rlog_all[0]
+        self.workers = [{k: getattr(self, k) for k in self.WORKER_ATTRS}]
+        self.workers[0]["dimg"] = self.dimg_all[0]
+        for q in range(1, W):
+            self.workers.append(self._alloc_worker(q, shards[q] if shards is not None else None))
+        self._log_args = O.round_log_args(self.rlog_all.view(-1), self.rblk, self.lbuf_all.view(-1), self.nv_all, W, 0,
+                                          self.weighting, 0.5 if self.loss == "mse" else 1.0,
+                                          losses_all=self.losses_all, alpha_all=self.alpha_all,
+                                          counters=self.dstate if self.graph else None)
+        self._sample_multi = self._masks_multi = None
+        if self.graph:      # the grouped round-start ops: job tables written to the device once, here
+            cs = [co for _, _, _, co, _ in D_CONVS]
+            jobs = []
+            for q, w in enumerate(self.workers):
+                for call, (ms, n) in enumerate(((w["mask_d"], B2), (w["mask_g"], B))):
+                    jobs += [(ms[k], n, cs[k], self.seed * 7919 + q, call * 4 + k) for k in range(4)]
+            self._masks_multi = O.DropoutMasksMulti(jobs, DROP_P, self.dstate[0:1], 8)
+            if shards is not None:
+                self._sample_multi = O.SampleRowsMulti(
+                    [(w["data"], self.seed + 1 + q, w["xin"], w["nv"] if w["short"] else None)
+                     for q, w in enumerate(self.workers)], B, self.dstate[0:1])
+
+    def _alloc_worker(self, q, data):
+        """Worker q > 0: the D-side buffers of the constructor again (same shapes), G's entries of the shared
+        dictionaries kept."""
+        B, B2, dev = self.B, 2 * self.B, self.device
+        e = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        dkeys = [bk for _, bk, _, _, _ in D_CONVS if bk]
+        w = dict(D=self.Ds[q], pk=_PackView(self.pk, q), xin=self.xin_rest[q - 1], rank=q, data=data)
+        w["q"] = [e(B2, hw // 2, hw // 2, co) for _, _, _, co, hw in D_CONVS]
+        w["r"] = [None] + [e(B2, hw // 2, hw // 2, co) for _, _, _, co, hw in D_CONVS[1:]]
+        w["flat"], w["v"] = e(B2, 512), e(B2, 1)
+        w["d_save"] = {bn: (e(2, co), e(2, co)) for _, bn, _, co, _ in D_CONVS if bn}
+        w["mask_d"] = [e(B2, co) for _, _, _, co, _ in D_CONVS]
+        w["mask_g"] = [e(B, co) for _, _, _, co, _ in D_CONVS]
+        w["dv"] = e(B2, 1)
+        w["dr"] = [None] + [e(B2, hw // 2, hw // 2, co) for _, _, _, co, hw in D_CONVS[1:]]
+        w["dc"] = [e(B2, hw // 2, hw // 2, co) for _, _, _, co, hw in D_CONVS]
+        w["dq1"] = e(B2, 16, 16, 16)
+        w["dimg"], w["lbuf"], w["nv"], w["rlog"] = self.dimg_all[q], self.lbuf_all[q], self.nv_all[q:q + 1], self.rlog_all[q]
+        w["hscr_d"], w["hscr_g"] = torch.zeros(B2 + 16, device=dev), torch.zeros(B + 16, device=dev)
+        w["dcoef"] = {bk: torch.zeros_like(t) for bk, t in self.dcoef.items()}
+        w["wws"] = {k: (torch.empty_like(t) if k in {c[0] for c in D_CONVS} else t) for k, t in self.wws.items()}
+        w["st_part"] = {k: (torch.zeros_like(t) if k in dkeys else t) for k, t in self.st_part.items()}
+        w["st_scratch"] = {k: (torch.zeros_like(t) if k in dkeys else t) for k, t in self.st_scratch.items()}
+        w["short"] = data is not None and data.shape[0] % B != 0
+        w["_short_call"], w["_perm"], w["_pos"], w["_nv_stale"] = False, None, 0, False
+        w["_gen"] = torch.Generator().manual_seed(self.seed + 1 + q)
+        w["_head_coef"], w["_d_folded"] = None, set()
+        return w
+
+    @contextlib.contextmanager
+    def _as_worker(self, q):
+        w = self.workers[q]
+        base = {k: self.__dict__[k] for k in self.WORKER_ATTRS}
+        if q == 0:
+            w.update(base, dimg=w["dimg"])
+        self.__dict__.update(w)
+        try:
+            yield
+        finally:
+            for k in self.WORKER_ATTRS:
+                w[k] = self.__dict__[k]
+            if q == 0:      # the step is worker 0: its sampler position etc. stay the step's own
+                base.update(w, dimg=base["dimg"])
+            self.__dict__.update(base)
 
     # ------------------------------------------------------------------ state
     def set_beta(self, beta=None):
@@ -389,9 +526,18 @@ class ConvGanStep:
         """capgan.py:28,156,309: torch.manual_seed(seed) then G (and D) constructed."""
         torch.manual_seed(seed_g)
         default_init(self.G)
-        if seed_d is not None:
-            torch.manual_seed(seed_d)
-        default_init(self.D)
+        if not self.colocated:
+            if seed_d is not None:
+                torch.manual_seed(seed_d)
+            default_init(self.D)
+            return
+        # co-located: one D per worker -- seed_d a list: worker q's seed; an int: every worker's (each worker process
+        # of the reference seeds alike); None: drawn one after the other from the stream G left
+        for q, d in enumerate(self.Ds):
+            sq = seed_d[q] if isinstance(seed_d, (list, tuple)) else seed_d
+            if sq is not None:
+                torch.manual_seed(sq)
+            default_init(d)
 
     # ------------------------------------------------------------------ resume
     def resume_state(self):
@@ -412,6 +558,18 @@ class ConvGanStep:
         out["sampler.pos"] = torch.tensor(self._pos, dtype=torch.long)
         out["sampler.perm"] = (self._perm.cpu().clone() if self._perm is not None else torch.zeros(0, dtype=torch.int32))
         out["sampler.gen"] = self._gen.get_state()
+        for q in range(1, self.colocated):     # the other co-located workers: their D and sampler ("D<q>", "sampler<q>")
+            w, fm = self.workers[q], self.Ds[q]
+            for k in ("p", "m", "v"):
+                out[f"D{q}.{k}"] = getattr(fm, k).detach().cpu().clone()
+            for k, v in fm.running.items():
+                out[f"D{q}.running.{k}"] = v.detach().cpu().clone()
+            out[f"D{q}.batches"] = torch.tensor([fm.batches[k] for k in fm.batches], dtype=torch.long)
+            out[f"D{q}.step"] = torch.tensor(fm.step, dtype=torch.long)
+            out[f"sampler{q}.pos"] = torch.tensor(w["_pos"], dtype=torch.long)
+            out[f"sampler{q}.perm"] = (w["_perm"].cpu().clone() if w["_perm"] is not None
+                                       else torch.zeros(0, dtype=torch.int32))
+            out[f"sampler{q}.gen"] = w["_gen"].get_state()
         return out
 
     @torch.no_grad()
@@ -430,9 +588,23 @@ class ConvGanStep:
         perm = sd["sampler.perm"]
         self._perm = perm.to(self.device) if perm.numel() else None
         self._gen.set_state(sd["sampler.gen"])
+        for q in range(1, self.colocated):
+            w, fm = self.workers[q], self.Ds[q]
+            for k in ("p", "m", "v"):
+                getattr(fm, k).copy_(sd[f"D{q}.{k}"])
+            for k, v in fm.running.items():
+                v.copy_(sd[f"D{q}.running.{k}"])
+            for k, b in zip(list(fm.batches), sd[f"D{q}.batches"].tolist()):
+                fm.batches[k] = int(b)
+            fm.step = int(sd[f"D{q}.step"])
+            w["_pos"] = int(sd[f"sampler{q}.pos"])
+            perm = sd[f"sampler{q}.perm"]
+            w["_perm"] = perm.to(self.device) if perm.numel() else None
+            w["_gen"].set_state(sd[f"sampler{q}.gen"])
         self._dstate_host = None            # rewritten from the host state by the next round
         self._lam_dev = None                # ... and the device lambda
-        self.rlog.zero_()                   # the records belong to the timeline that was running here
+        # the records belong to the timeline that was running here
+        (self.rlog_all if self.colocated else self.rlog).zero_()
         torch.cuda.current_stream().synchronize()
 
     # ------------------------------------------------------------------ pieces
@@ -448,7 +620,7 @@ class ConvGanStep:
         idx = self._perm[self._pos:self._pos + take]
         if take < B:
             idx = torch.cat([idx, idx[:1].expand(B - take)])
-        O.gather_rows(self.data, idx, 0, B, 1024, self.x3)
+        O.gather_rows(self.data, idx, 0, B, 1024, self.xin)
         if self.short or self._nv_stale:
             self.nv.fill_(take)
             self._nv_stale = False
@@ -658,8 +830,14 @@ class ConvGanStep:
             if counters:     # round, G steps, D steps += 1 in the deferred launch; G's completed steps -> dstate[4]
                 O.defer_counters(self.dstate[0:3], self.dstate[4:5], 1)
             if self.wdefer:
-                O.round_log(self._log_args, **host)
+                self._round_log(host)
         if not self.wdefer:
+            self._round_log(host)
+
+    def _round_log(self, host):
+        if self.colocated:      # W records, one ring per worker; lambda advances once
+            O.round_log_group(self._log_args, self.colocated, **host)
+        else:
             O.round_log(self._log_args, **host)
 
     def _g_backward_ops(self):
@@ -737,16 +915,22 @@ class ConvGanStep:
         # every op of the phase runs on the current stream, with this step's MFMA operand type (the thread's mode
         # is restored on exit; a captured phase keeps the kernels of the type it was captured with)
         with O.mma_dtype(self.gemm_dtype), O.stream_cache():
-            self._phase_a(real)
+            if self.colocated:
+                self._phase_a_co(real)
+            else:
+                self._phase_a(real)
 
-    def _round_start(self, real):
-        B = self.B
+    def _draw_z(self):
         if self.gen_z:
             if self.graph:
                 O.normal_fill_dev(self.z, self.seed, self.dstate[0:1])
             else:
                 C.check(C.lib.cgl_normal_fill(ctypes_ptr(self.z), self.z.numel(), self.seed, self.round, 0,
                                               O._s()), "cgl_normal_fill")
+
+    def _real_batch(self, real):
+        """This worker's real rows of the round into ``xin``: an explicit batch, else the shard's sampler."""
+        B = self.B
         self._short_call = self.short
         if real is not None:
             # an explicit real batch; fewer than B rows = a short batch (padding rows repeat its first row)
@@ -754,25 +938,99 @@ class ConvGanStep:
             nr = real.shape[0]
             if not 1 <= nr <= B:
                 raise ValueError(f"real batch of {nr} rows: expected 1 .. {B}")
-            O.gather_rows(real, None, 0, nr, 1024, self.x3)
+            O.gather_rows(real, None, 0, nr, 1024, self.xin)
             if nr < B:
                 O.gather_rows(real, torch.zeros(B - nr, dtype=torch.int32, device=self.device), 0, B - nr, 1024,
-                              self.x3[nr:])
+                              self.xin[nr:])
             self._short_call = nr < B or self.short
             if self._short_call or self._nv_stale:     # (stale: the round log records nv of full batches too)
                 self.nv.fill_(nr)
                 self._nv_stale = nr < B
         elif self.data is not None:
             if self.graph:
-                O.sample_rows_dev(self.data, B, self.seed + 1 + self.rank, self.dstate[0:1], self.x3,
+                O.sample_rows_dev(self.data, B, self.seed + 1 + self.rank, self.dstate[0:1], self.xin,
                                   nv_out=self.nv if self.short else None)
             else:
                 self._sample_real()
+
+    def _round_start(self, real):
+        self._draw_z()
+        self._real_batch(real)
         self.pk.run()
         self._masks()
 
+    def _round_start_co(self, reals):
+        """The co-located round start: z once; every worker's real batch (graph rounds: one grouped sampler job),
+        the first weight-pack launch (G and D0) and every worker's eight masks (graph rounds: one grouped job)."""
+        W = self.colocated
+        self._draw_z()
+        if reals is None and self._sample_multi is not None:
+            self._short_call = self.short
+            for w in self.workers[1:]:
+                w["_short_call"] = w["short"]
+            self._sample_multi()
+        else:
+            for q in range(W):
+                with self._as_worker(q):
+                    self._real_batch(None if reals is None else reals[q])
+        self.pk.run(self._pack_chunks[0])
+        if self._masks_multi is not None:
+            self._masks_multi()
+        else:
+            for q in range(W):
+                with self._as_worker(q):
+                    self._masks()
+
+    def _phase_a_co(self, reals=None):
+        B, W = self.B, self.colocated
+        if reals is not None and len(reals) != W:
+            raise ValueError(f"reals: one real batch per worker ({W})")
+        if self.graph:
+            self._sync_dstate()
+        self._sync_lam()         # the exchange launch reads the device lambda
+        self._mark("start")
+        with O.launch_batch(self.graph and reals is None and self.batch_on):
+            self._round_start_co(reals)
+        for name in self._pack_chunks[1:]:     # the discriminators past the first launch's 48 problems
+            self.pk.run(name)
+        self._g_forward()                      # once: Xd, Xg
+        O.bcast_rows(self.x3[B:2 * B], self.xin_rest[0][B:], 2 * B * 1024, W - 1)
+        self._mark("g_forward")
+        for q in range(W):
+            with self._as_worker(q):
+                self._worker_pass()
+        self._mark("d_workers")
+        O.alpha_combine(self.weighting, self.beta, self.lbuf_all.view(-1)[2:], 8, self.rblk,
+                        self.dimg_all.view(W, -1), self.dimg, self.alpha_all, self.losses_all)
+        self._mark("exchange")
+
+    _marks = None
+
+    def _mark(self, name):
+        if self._marks is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self._marks.append((name, ev))
+
+    def profile_round(self):
+        """One eager co-located round with events between its parts: microseconds of ``g_forward`` (round start, G
+        forward, the Xd copies), ``d_workers`` (the W D steps and G-loss passes), ``exchange`` (the alpha / combine
+        launch) and ``g_backward`` (G backward, round log, G Adam).  The round counts (state advances); launches go
+        out one by one, so launch-bound parts read longer here than inside a graph."""
+        if not self.colocated:
+            raise ValueError("profile_round: a co-located step's round")
+        self._marks = []
+        try:
+            self.phase_a(None)
+            self.phase_b()
+            self._mark("g_backward")
+            torch.cuda.current_stream().synchronize()
+            ev = self._marks
+            return {b[0]: a[1].elapsed_time(b[1]) * 1e3 for a, b in zip(ev, ev[1:])}
+        finally:
+            self._marks = None
+
     def _phase_a(self, real=None):
-        B = self.B
         if self.graph:
             self._sync_dstate()
         # graph rounds: the z draw, the sampler, the weight packing and the Dropout2d masks (independent, all
@@ -780,10 +1038,15 @@ class ConvGanStep:
         with O.launch_batch(self.graph and real is None and self.batch_on):
             self._round_start(real)
         self._g_forward()
+        self._worker_pass()
+
+    def _worker_pass(self):
+        """One worker's D step, D Adam, D re-pack and G-loss pass on its buffers, ending in its ``dimg``."""
+        B = self.B
         # local D step on [real; Xd]: two forward calls (statistics, masks per call), one backward
         half = 0.5 if self.loss == "mse" else 1.0
         nvd = self.nv if self._short_call else None     # the real call's images (short final batch)
-        self._d_forward(self.x3, 2 * B, 2, self.mask_d, nvalid=nvd)
+        self._d_forward(self.xin, 2 * B, 2, self.mask_d, nvalid=nvd)
         if self.head_fuse:
             self._head(2 * B, [(B, 1, half, self.lbuf[0:1], nvd), (B, 0, half, self.lbuf[1:2], None)], self.hscr_d,
                        self.flat)
@@ -791,7 +1054,7 @@ class ConvGanStep:
             with O.launch_batch(self.batch_on):     # the real and fake heads: one launch
                 O.adv_loss(self.v[:B], B, 1, self.loss, 1, half, self.lbuf[0:1], self.dv[:B], nvalid=nvd)
                 O.adv_loss(self.v[B:2 * B], B, 1, self.loss, 0, half, self.lbuf[1:2], self.dv[B:2 * B])
-        self._d_backward(self.x3, 2 * B, 2, self.mask_d, wgrad=True, dx=None, nvalid=nvd)
+        self._d_backward(self.xin, 2 * B, 2, self.mask_d, wgrad=True, dx=None, nvalid=nvd)
         self.D.adam(self.lr, self.betas, self.eps, step_dev=self.dstate[2:3] if self.graph else None)
         self.pk.run("D")
         # G loss through the updated D (its D weight gradient is discarded by the reference: skipped)
@@ -823,11 +1086,18 @@ class ConvGanStep:
         if self.weighting != "mean":     # MD-GAN's server has no lambda (MDGAN/MNIST/mdgan.py:203-205)
             self.lam = float(np.float32(self.lam) + np.float32(-0.1) * np.float32(-0.001))
 
-    def run(self, real=None, eager=False):
+    def run(self, real=None, eager=False, reals=None):
         """One round with N = 1 (alpha = 1 exactly, capgan.py:247-248).  With graph=True (and the
         round drawing its own real batch) the first round runs eagerly, the second is captured into a
-        hipGraph and every round from then on is one replay."""
-        if self.n_workers != 1:
+        hipGraph and every round from then on is one replay.  A co-located step runs its whole W-worker round the
+        same way; ``reals`` = one explicit real batch per worker (each may be short)."""
+        if self.colocated:
+            if real is not None:
+                raise ValueError("a co-located step takes reals=[one batch per worker]")
+            real = reals
+        elif reals is not None:
+            raise ValueError("reals= is for a co-located step")
+        elif self.n_workers != 1:
             raise RuntimeError("n_workers > 1: use cglgan.exchange.ConvWorkerExchange")
         if not self.graph or eager or real is not None or self.data is None or self.round == 0:
             self.phase_a(real)
@@ -846,7 +1116,8 @@ class ConvGanStep:
         graph-launch boundary between them); otherwise ``rounds`` calls of ``run()``."""
         if rounds <= 0:
             return
-        if not self.graph or self.data is None or self.round == 0 or rounds == 1 or self.n_workers != 1:
+        if (not self.graph or self.data is None or self.round == 0 or rounds == 1 or
+                (self.n_workers != 1 and not self.colocated)):
             for _ in range(rounds):
                 self.run()
             return
@@ -887,11 +1158,7 @@ class ConvGanStep:
                 self.phase_a(None)
                 self.phase_b()
         # capturing issued nothing: restore the host bookkeeping (run_rounds applies the delta per replayed round)
-        self.round, self.G.step, self.D.step = before[0], before[1], before[2]
-        self.G.batches.update(before[3])
-        self.D.batches.update(before[4])
-        self.lam = self._lam_dev = before[5]
-        self._dstate_host = (self.round, self.G.step, self.D.step)
+        self._restore_host(before)
         return g
 
     # ------------------------------------------------------------------ split round (N > 1)
@@ -923,6 +1190,16 @@ class ConvGanStep:
     def _host_state(self):
         return (self.round, self.G.step, self.D.step, dict(self.G.batches), dict(self.D.batches), self.lam)
 
+    def _restore_host(self, before):
+        """The host bookkeeping as ``_host_state`` recorded it (every co-located D counts with worker 0's)."""
+        self.round, self.G.step = before[0], before[1]
+        self.G.batches.update(before[3])
+        for d in self.Ds:
+            d.step = before[2]
+            d.batches.update(before[4])
+        self.lam = self._lam_dev = before[5]
+        self._dstate_host = (self.round, self.G.step, self.D.step)
+
     def _sync_dstate(self):
         """dstate must hold (round, G steps, D steps) of the host: rewritten only when the host state
         moved without it (a load_state_dict, a round of another path)."""
@@ -930,6 +1207,10 @@ class ConvGanStep:
         if want != self._dstate_host:
             self.dstate[:3].copy_(torch.tensor(want, dtype=torch.int32))
             self._dstate_host = want
+        for w in (self.workers or ())[1:]:     # (co-located: the other workers' counts; worker 0's is the step's own)
+            if w["_nv_stale"] and not w["short"]:
+                w["nv"].fill_(self.B)
+                w["_nv_stale"] = False
         if self._nv_stale and not self.short:     # (a ragged shard's sampler rewrites nv every round itself)
             self.nv.fill_(self.B)
             self._nv_stale = False
@@ -959,11 +1240,7 @@ class ConvGanStep:
                 self.phase_b()
         after = self._host_state()
         # capturing issued nothing: restore the host bookkeeping, remember what one round adds
-        self.round, self.G.step, self.D.step = before[0], before[1], before[2]
-        self.G.batches.update(before[3])
-        self.D.batches.update(before[4])
-        self.lam = self._lam_dev = before[5]
-        self._dstate_host = (self.round, self.G.step, self.D.step)
+        self._restore_host(before)
         self._graph_delta = ({k: after[3][k] - before[3][k] for k in before[3]},
                              {k: after[4][k] - before[4][k] for k in before[4]})
         if split:
@@ -975,17 +1252,26 @@ class ConvGanStep:
         gb, db = self._graph_delta
         for k, v in gb.items():
             self.G.batches[k] += v
-        for k, v in db.items():
-            self.D.batches[k] += v
+        for d in self.Ds:
+            for k, v in db.items():
+                d.batches[k] += v
+            d.step += 1
         self.G.step += 1
-        self.D.step += 1
         self._lam_step()
         self._lam_dev = self.lam
         self.round += 1
         self._dstate_host = (self.round, self.G.step, self.D.step)
 
-    def stats(self):
-        l = self.lbuf.cpu()
+    def _worker_index(self, worker):
+        worker = int(worker)
+        if not 0 <= worker < max(self.colocated, 1):
+            raise ValueError(f"worker {worker}: this step holds {max(self.colocated, 1)}")
+        return worker
+
+    def stats(self, worker=0):
+        """``worker``: which co-located worker's losses (0: the step's own)."""
+        worker = self._worker_index(worker)
+        l = (self.lbuf_all[worker] if self.colocated else self.lbuf).cpu()
         half = 0.5 if self.loss == "mse" else 1.0
         return {"round": self.round, "d_real": float(l[0]), "d_fake": float(l[1]),
                 "d_loss": float((l[0] + l[1]) * half), "g_loss": float(l[2]), "lambda": self.lam,
@@ -997,19 +1283,22 @@ class ConvGanStep:
         """Rounds the device round log keeps (a ring: round r overwrites round r - log_capacity)."""
         return C.lib.cgl_conv_round_log_capacity()
 
-    def losses_log(self, first: int, count: int):
+    def losses_log(self, first: int, count: int, worker: int = 0):
         """The scalars of rounds ``first`` .. ``first + count - 1`` (1-based, as ``stats()["round"]`` after each), one
         dict per round, read from the device round log with one copy (two when the range wraps in the ring) and
         one stream synchronise -- what the reference prints after every communication round (capgan.py:177-183),
         also for the rounds inside a ``run_rounds`` launch.  Keys: ``round, d_real, d_fake, d_loss, g_loss, alpha,
         F, lambda, real_rows, g_step, d_step``.  LookupError when a round of the range is not in the log (not run
         yet, overwritten, or cleared by ``load_resume_state``); ValueError for a range no read can take."""
-        return self.log_dicts(self.read_log(first, count))
+        return self.log_dicts(self.read_log(first, count, worker))
 
-    def read_log(self, first: int, count: int):
+    def read_log(self, first: int, count: int, worker: int = 0):
         """The raw records (``_lib.ConvRoundRec`` array, a host copy of its own) of ``losses_log``'s range: the
-        device read without the conversion, for a caller that formats them later (``log_dicts``)."""
+        device read without the conversion, for a caller that formats them later (``log_dicts``).  ``worker``: the
+        co-located worker whose ring is read (its losses, alpha and real rows; F, lambda and the counts are shared)."""
         first, count = int(first), int(count)
+        worker = self._worker_index(worker)
+        ring = self.rlog_all[worker] if self.colocated else self.rlog
         cap = self.log_capacity
         if first < 1 or count < 1 or count > cap:
             raise ValueError(f"rounds {first}..{first + count - 1}: rounds are numbered from 1 and one read takes "
@@ -1017,7 +1306,7 @@ class ConvGanStep:
         if self._log_host is None:     # page-locked: the copy goes straight to it, no staging
             self._log_host = torch.empty(cap * ctypes.sizeof(C.ConvRoundRec), dtype=torch.uint8, pin_memory=True)
         buf = (C.ConvRoundRec * count).from_address(self._log_host.data_ptr())
-        rc = C.lib.cgl_conv_read_round_log(ctypes_ptr(self.rlog), first, count, buf,
+        rc = C.lib.cgl_conv_read_round_log(ctypes_ptr(ring), first, count, buf,
                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         if rc == -2:
             raise LookupError(f"rounds {first}..{first + count - 1} are not all in the round log (capacity {cap} "
@@ -1042,3 +1331,19 @@ class ConvGanStep:
 
 def ctypes_ptr(t):
     return ctypes.c_void_p(t.data_ptr())
+
+
+class _PackView:
+    """Co-located worker q's view of the step's PackSet: D's operands under the one-worker keys (``view["model.3f"]``
+    is PackSet["<q>:model.3f"]) and ``run("D")`` packing that worker's discriminator."""
+
+    def __init__(self, pk, q):
+        self._pk, self._q = pk, q
+
+    def __getitem__(self, key):
+        return self._pk[f"{self._q}:{key}"]
+
+    def run(self, group):
+        if group != "D":
+            raise ValueError("a worker's pack view packs its own discriminator only")
+        self._pk.run(f"D{self._q}")

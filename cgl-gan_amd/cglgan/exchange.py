@@ -632,3 +632,61 @@ class ConvLocalComm:
                 tot /= self.size
                 for t in ts:
                     t.copy_(tot)
+
+
+class ConvColocatedExchange:
+    """The round loop of a co-located conv step (``ConvGanStep(colocated=W)``: one G and the server's W discriminators
+    in one context, the alpha exchange inside the round) with ``ConvWorkerExchange``'s ``round`` / ``rounds``
+    interface.  What is left to exchange is D: the E-share every ``share_every`` rounds -- D's flat parameters and
+    every BatchNorm running statistic averaged over the W workers with ``ConvLocalComm``'s arithmetic (sum in worker
+    order, divide by W, written to all).  ``rounds`` issues the step's multi-round launches cut after every share
+    round (``chunks``, as ``ColocatedExchange``).  No D-swap yet."""
+
+    comm = None
+
+    def __init__(self, step, share_every: int = 0):
+        W = int(getattr(step, "colocated", 0) or 0)
+        if W < 2:
+            raise ValueError("ConvColocatedExchange drives a co-located step (ConvGanStep(colocated=W), W >= 2)")
+        self.step, self.size, self.share_every = step, W, int(share_every)
+
+    def _due(self, r):
+        return self.share_every > 0 and (r + 1) % self.share_every == 0
+
+    def chunks(self, r0: int, n: int):
+        """Rounds r0 .. r0 + n - 1 as launch lengths: a launch ends with the first of its rounds after which D is
+        shared.  The lengths sum to n."""
+        out, run = [], 0
+        for r in range(r0, r0 + max(0, int(n))):
+            run += 1
+            if self._due(r):
+                out.append(run)
+                run = 0
+        if run:
+            out.append(run)
+        return out
+
+    @torch.no_grad()
+    def _d_exchange(self, r):
+        if not self._due(r):
+            return
+        Ds = self.step.Ds
+        for i in range(1 + len(Ds[0].running)):
+            ts = [d.p if i == 0 else list(d.running.values())[i - 1] for d in Ds]
+            tot = ts[0].clone()
+            for t in ts[1:]:
+                tot += t
+            tot /= self.size
+            for t in ts:
+                t.copy_(tot)
+
+    def round(self, r: int, reals=None, eager=False):
+        self.step.run(reals=reals, eager=eager)
+        self._d_exchange(r)
+
+    def rounds(self, r0: int, n: int):
+        r = r0
+        for m in self.chunks(r0, n):
+            self.step.run_rounds(m)
+            r += m
+            self._d_exchange(r - 1)

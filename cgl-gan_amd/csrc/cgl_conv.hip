@@ -1136,6 +1136,7 @@ struct CglWgradReduceMulti {
   // exists for the record alone when cnt == null); lg.counters: where the block reads the round and step counts
   // (== cnt when both are recorded), null: the host integers of lg
   cgl_conv_round_log_args lg;
+  int lg_group;     // > 1: the grouped record of that many co-located workers (cgl_conv_wgrad_defer_log_group)
 };
 
 // The conv round's log record (cgl_conv_round_rec) and the device Lambda's step, by 16 lanes of one wave: every lane
@@ -1147,13 +1148,15 @@ struct CglWgradReduceMulti {
 // advances the counters.  Two halves, so that the deferred launch issues the record's loads together with its
 // counter reads (one memory round trip before the barrier) and only stores after it:
 // cgl_conv_log_word: lane l's word of the record (and the advanced Lambda); cgl_conv_log_store: the stores.
-__device__ __forceinline__ unsigned cgl_conv_log_word(const cgl_conv_round_log_args& a, int rnd, int gs, int ds, int lane,
-                                                      float& lam_out) {
+// (lbuf, nvp, rank: a.lbuf, a.nv, a.rank for the one record of a context; worker q's words for a grouped record)
+__device__ __forceinline__ unsigned cgl_conv_log_word_at(const cgl_conv_round_log_args& a, const float* lbuf,
+                                                         const int* nvp, int rank, int rnd, int gs, int ds, int lane,
+                                                         float& lam_out) {
 #pragma clang fp contract(off)
   const int N = a.n_workers;
-  const float d_real = gld(a.lbuf), d_fake = gld(a.lbuf + 1), g = gld(a.lbuf + 2);
+  const float d_real = gld(lbuf), d_fake = gld(lbuf + 1), g = gld(lbuf + 2);
   const float lam = gld(a.lam_dev);
-  const int nv = gldi(a.nv);
+  const int nv = gldi(nvp);
   const bool mean = a.weighting == CGL_W_MEAN;
   float s = 0.f, alpha = 1.f, F;
   if (N == 1) {
@@ -1163,7 +1166,7 @@ __device__ __forceinline__ unsigned cgl_conv_log_word(const cgl_conv_round_log_a
       const float lq = gld(a.losses_all + q);
       s = mean ? s + lq : fmaf(gld(a.alpha_all + q), lq, s);
     }
-    alpha = gld(a.alpha_all + a.rank);
+    alpha = gld(a.alpha_all + rank);
   }
   F = mean ? s / N : fmaf(-0.001f, lam, s);
   // optim.SGD([Lambda], lr=0.1) with dF/dLambda = -0.001 (capgan.py:249,259); MD-GAN's mean has no Lambda
@@ -1184,12 +1187,36 @@ __device__ __forceinline__ unsigned cgl_conv_log_word(const cgl_conv_round_log_a
   lam_out = lam_new;
   return w;
 }
+__device__ __forceinline__ unsigned cgl_conv_log_word(const cgl_conv_round_log_args& a, int rnd, int gs, int ds, int lane,
+                                                      float& lam_out) {
+  return cgl_conv_log_word_at(a, a.lbuf, a.nv, a.rank, rnd, gs, ds, lane, lam_out);
+}
 __device__ __forceinline__ void cgl_conv_log_store(const cgl_conv_round_log_args& a, int rnd, int lane, unsigned w,
                                                    float lam_new) {
   static_assert(sizeof(cgl_conv_round_rec) == 64, "cgl_conv_round_rec: one 64-byte line (ABI)");
   cgl_gu32* rec = (cgl_gu32*)(a.ring + ((unsigned)(rnd - 1) % CGL_CONV_ROUND_LOG_CAP));
   rec[lane] = w;
   if (lane == 0) gst(a.lam_dev, lam_new);
+}
+
+// The grouped record (co-located workers, cgl_conv_round_log_group): thread t = 16 q + lane holds lane's word of worker
+// q's record -- cgl_conv_log_word with rank = q on worker q's loss words and image count -- and stores it into ring q
+// of [W][CGL_CONV_ROUND_LOG_CAP]; W <= 16, so one 256-thread workgroup.  Lambda advances once (thread 0); the caller
+// puts a barrier between the two halves, so every worker's lanes read Lambda before that store.
+__device__ __forceinline__ unsigned cgl_conv_log_group_word(const cgl_conv_round_log_args& a, int W, int rnd, int gs,
+                                                            int ds, int t, float& lam_out) {
+  const int q = t >> 4;
+  lam_out = 0.f;
+  if (q >= W) return 0u;
+  return cgl_conv_log_word_at(a, a.lbuf + 8 * q, a.nv + q, q, rnd, gs, ds, t & 15, lam_out);
+}
+__device__ __forceinline__ void cgl_conv_log_group_store(const cgl_conv_round_log_args& a, int W, int rnd, int t,
+                                                         unsigned w, float lam_new) {
+  const int q = t >> 4;
+  if (q >= W) return;
+  cgl_gu32* rec = (cgl_gu32*)(a.ring + (size_t)q * CGL_CONV_ROUND_LOG_CAP + ((unsigned)(rnd - 1) % CGL_CONV_ROUND_LOG_CAP));
+  rec[t & 15] = w;
+  if (t == 0) gst(a.lam_dev, lam_new);
 }
 
 __global__ __launch_bounds__(64) void cgl_conv_round_log_k(cgl_conv_round_log_args a) {
@@ -1202,8 +1229,11 @@ __global__ __launch_bounds__(64) void cgl_conv_round_log_k(cgl_conv_round_log_ar
   }
 }
 
-__global__ __launch_bounds__(256) void cgl_conv_wgrad_reduce_multi(CglWgradReduceMulti m) {
-  __shared__ double red[256];
+// GROUP: the record block writes the grouped record of m.lg_group co-located workers (thread 16 q + lane, all 256
+// threads) -- the launch of a co-located step's G backward (cgl_conv_wgrad_reduce_multi_grp); every other block is
+// the same.  A template, so that the one-worker launch's kernel is compiled from what it was compiled from before.
+template <bool GROUP>
+__device__ __forceinline__ void cgl_conv_wgrad_reduce_multi_body(const CglWgradReduceMulti& m, double* red) {
   const int b = blockIdx.x, n = m.n;
   const int fend = m.begin[n] + m.c1_blocks + m.fbeg[m.nfin];
   if (b >= fend + m.d1_blocks) {     // the counters / round-log block
@@ -1215,16 +1245,24 @@ __global__ __launch_bounds__(256) void cgl_conv_wgrad_reduce_multi(CglWgradReduc
     }
     // the record on 16 lanes of the second wave, off the counters lanes' chain (the launch's tail): its loads go out
     // beside the counter reads, its stores after the barrier beside the add
-    const bool logl = m.lg.ring && t >= 64 && t < 80;
+    const bool logl = m.lg.ring && (GROUP || (t >= 64 && t < 80));
     unsigned lw = 0u;
     float lam_new = 0.f;
-    if (logl) lw = cgl_conv_log_word(m.lg, rnd, gs, ds, t - 64, lam_new);
+    if constexpr (GROUP) {
+      if (logl) lw = cgl_conv_log_group_word(m.lg, m.lg_group, rnd, gs, ds, t, lam_new);
+    } else {
+      if (logl) lw = cgl_conv_log_word(m.lg, rnd, gs, ds, t - 64, lam_new);
+    }
     __syncthreads();                 // (every lane has read the counters before lane 0..n-1 add)
     if (m.cnt) {
       if (t == 0) *m.cnt_snap = snap;
       if (t < m.cnt_n) m.cnt[t] += m.cnt_v;
     }
-    if (logl) cgl_conv_log_store(m.lg, rnd, t - 64, lw, lam_new);
+    if constexpr (GROUP) {
+      if (logl) cgl_conv_log_group_store(m.lg, m.lg_group, rnd, t, lw, lam_new);
+    } else {
+      if (logl) cgl_conv_log_store(m.lg, rnd, t - 64, lw, lam_new);
+    }
     return;
   }
   if (b >= fend) {
@@ -1247,6 +1285,14 @@ __global__ __launch_bounds__(256) void cgl_conv_wgrad_reduce_multi(CglWgradReduc
   else if (n > 2 && b >= m.begin[2]) cgl_conv_wgrad_reduce_at(m.r[2], b - m.begin[2], red);
   else if (n > 1 && b >= m.begin[1]) cgl_conv_wgrad_reduce_at(m.r[1], b - m.begin[1], red);
   else cgl_conv_wgrad_reduce_at(m.r[0], b, red);
+}
+__global__ __launch_bounds__(256) void cgl_conv_wgrad_reduce_multi(CglWgradReduceMulti m) {
+  __shared__ double red[256];
+  cgl_conv_wgrad_reduce_multi_body<false>(m, red);
+}
+__global__ __launch_bounds__(256) void cgl_conv_wgrad_reduce_multi_grp(CglWgradReduceMulti m) {
+  __shared__ double red[256];
+  cgl_conv_wgrad_reduce_multi_body<true>(m, red);
 }
 
 // Input gradient of a one-output Linear over a flattened NCHW feature map (the discriminator head,
@@ -1296,6 +1342,15 @@ struct CglMasksArgs {
   unsigned long long rstride;
 };
 
+// element i of a mask drawn with (seed, ctr): shared by the single-seed and the per-mask-seed launches
+__device__ __forceinline__ void cgl_dropout_mask_elem(float* mask, long i, unsigned long long seed,
+                                                      unsigned long long ctr, float keep, float scale) {
+  uint32_t c[4] = {(uint32_t)i, (uint32_t)(i >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32) ^ 0x5bd1e995u};
+  cgl_philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const float u = (float)(c[0] >> 8) * (1.0f / 16777216.0f);
+  gst(mask + i, u < keep ? scale : 0.f);
+}
+
 __device__ __forceinline__ void cgl_dropout_masks_at(const CGL_AS4 CglMasksArgs* A, int b) {
   int q = 0;
   for (int j = 1; j < A->nm; ++j)
@@ -1304,10 +1359,7 @@ __device__ __forceinline__ void cgl_dropout_masks_at(const CGL_AS4 CglMasksArgs*
   if (i >= A->n[q]) return;
   const unsigned long long ctr = A->ctr[q] + (A->rdev ? A->rstride * (unsigned long long)gldi(A->rdev) : 0ull),
                            seed = A->seed;
-  uint32_t c[4] = {(uint32_t)i, (uint32_t)(i >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32) ^ 0x5bd1e995u};
-  cgl_philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const float u = (float)(c[0] >> 8) * (1.0f / 16777216.0f);
-  gst(A->mask[q] + i, u < A->keep ? A->scale : 0.f);
+  cgl_dropout_mask_elem(A->mask[q], i, seed, ctr, A->keep, A->scale);
 }
 
 __global__ __launch_bounds__(256) void cgl_dropout_masks_k(CglMasksArgs) {
@@ -1527,6 +1579,159 @@ __global__ __launch_bounds__(256) void cgl_conv_begin_k(CglConvBeginArgs) {
 
 __global__ __launch_bounds__(64) void cgl_counters_add_k(int* p, int n, int v) {
   if ((int)threadIdx.x < n) p[threadIdx.x] += v;
+}
+
+// ------------------------------------------------------------------------------------------
+// Co-located conv workers (ConvGanStep(colocated=W)): the per-worker start-of-round ops of W workers as one launch
+// each, from job tables in device memory (written once by the _prepare calls; W x 8 masks do not fit the batched
+// launch's argument segment).  Every workgroup runs the single op's own body on its job, so the results are bitwise
+// the W single calls.  The tables carry their own counts: a workgroup past them does nothing.
+struct CglSampleTab {
+  int njobs, nrows, rowf, pad;
+  cgl_sample_job j[CGL_MAX_COLOCATED];
+};
+__device__ __forceinline__ void cgl_sample_multi_at(const CglSampleTab* T, const int* round, int b) {
+  const CGL_GLOBAL CglSampleTab* G = (const CGL_GLOBAL CglSampleTab*)T;
+  const int nrows = G->nrows;
+  const int q = b / nrows, r = b - q * nrows;
+  if (q >= G->njobs) return;
+  const CGL_GLOBAL cgl_sample_job* J = &G->j[q];
+  cgl_sample_rows_at(J->src, J->n_src, nrows, G->rowf, J->seed, round, J->dst, J->nv_out, r);
+}
+__global__ __launch_bounds__(256) void cgl_sample_rows_multi_k(const CglSampleTab* T, const int* round) {
+  cgl_sample_multi_at(T, round, (int)blockIdx.x);
+}
+
+struct CglMaskJobK {
+  float* mask;
+  long n;
+  unsigned long long seed, ctr;
+  int blk_begin, pad;
+};
+struct CglMasksTab {
+  int nm, blocks;
+  float keep, scale;
+  CglMaskJobK j[CGL_MASKS_MULTI_MAX];
+};
+__device__ __forceinline__ void cgl_masks_multi_at(const CglMasksTab* T, const int* rdev, unsigned long long rstride,
+                                                   int b) {
+  const CGL_GLOBAL CglMasksTab* G = (const CGL_GLOBAL CglMasksTab*)T;
+  if (b >= G->blocks) return;
+  int lo = 0, hi = G->nm - 1;          // the last job whose first block is <= b (uniform per workgroup)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (b >= G->j[mid].blk_begin) lo = mid; else hi = mid - 1;
+  }
+  const CGL_GLOBAL CglMaskJobK* J = &G->j[lo];
+  const long i = (long)(b - J->blk_begin) * 256 + threadIdx.x;
+  if (i >= J->n) return;
+  cgl_dropout_mask_elem(J->mask, i, J->seed, J->ctr + rstride * (unsigned long long)gldi(rdev), G->keep, G->scale);
+}
+__global__ __launch_bounds__(256) void cgl_dropout_masks_multi_k(const CglMasksTab* T, const int* rdev,
+                                                                 unsigned long long rstride) {
+  cgl_masks_multi_at(T, rdev, rstride, (int)blockIdx.x);
+}
+
+// The batched round start with grouped jobs: cgl_conv_begin_k's parts, then [grouped masks | grouped sampler].  A
+// kernel of its own, launched only when a batch holds a grouped job, so the one-worker round keeps its launch.
+struct CglConvBeginMultiArgs {
+  CglConvBeginArgs base;
+  const CglMasksTab* mm_tab; const int* mm_round; unsigned long long mm_stride; int mmb;
+  const CglSampleTab* sm_tab; const int* sm_round; int smb;
+};
+static_assert(sizeof(CglConvBeginMultiArgs) <= 4096, "the batched launch's arguments must fit the kernarg segment");
+__global__ __launch_bounds__(256) void cgl_conv_begin_multi_k(CglConvBeginMultiArgs) {
+  typedef const CGL_AS4 CglConvBeginMultiArgs* KA;
+  const KA A = (KA)__builtin_amdgcn_kernarg_segment_ptr();
+  int b = blockIdx.x;
+  if (b < A->base.pb) { cgl_conv_pack_at(&A->base.pack, b); return; }
+  b -= A->base.pb;
+  if (b < A->base.mb) { cgl_dropout_masks_at(&A->base.masks, b); return; }
+  b -= A->base.mb;
+  if (b < A->base.nb) {
+    cgl_normal_at((long)b * 256 + threadIdx.x, A->base.n_out, A->base.n_n, A->base.n_seed,
+                  (uint32_t)gldi(A->base.n_round), A->base.n_sid);
+    return;
+  }
+  b -= A->base.nb;
+  if (b < A->base.sb) {
+    cgl_sample_rows_at(A->base.s_src, A->base.s_nsrc, A->base.s_nrows, A->base.s_rowf, A->base.s_seed,
+                       A->base.s_round, A->base.s_dst, A->base.s_nv, b);
+    return;
+  }
+  b -= A->base.sb;
+  if (b < A->base.lb) {
+    const CGL_AS4 CglAdvArgs* q = &A->base.adv[b];
+    cgl_adv_loss_at(q->x, q->Mall, q->C, q->loss, q->target, q->weight, q->loss_out, q->grad, q->nv);
+    return;
+  }
+  b -= A->base.lb;
+  if (b < A->mmb) { cgl_masks_multi_at(A->mm_tab, A->mm_round, A->mm_stride, b); return; }
+  b -= A->mmb;
+  cgl_sample_multi_at(A->sm_tab, A->sm_round, b);
+}
+
+// dst0[q * stride + i] = src[i], q < copies: the shared Xd behind every co-located worker's real rows.  float4.
+__global__ __launch_bounds__(256) void cgl_bcast_rows_k(const float* src, long n4, float* dst0, long stride4,
+                                                        int copies) {
+  gcf4p s4 = (gcf4p)src;
+  gf4p d4 = (gf4p)dst0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const f32x4 v = s4[i];
+    for (int q = 0; q < copies; ++q) d4[q * stride4 + i] = v;
+  }
+}
+
+// The co-located exchange: alpha from the W G losses and the device Lambda (cgl_weights, computed per workgroup as
+// cgl_weights_scale_k does), then the alpha-weighted sum of the W image gradients in worker order -- each product
+// rounded before its add, as W cgl_weights_scale launches (x *= alpha) followed by the rank-order sum round.
+struct CglCombineArgs {
+  int mode, W, gstride, pad;
+  float beta[CGL_MAX_COLOCATED];
+  const float* gloss; const float* lam; const float* d; float* out; float* alpha_all; float* losses_all;
+  long nx4;
+};
+__global__ __launch_bounds__(256) void cgl_conv_alpha_combine_k(CglCombineArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float s_l[CGL_MAX_WORKERS], s_al[CGL_MAX_WORKERS], s_t[2][CGL_MAX_WORKERS];
+  const int W = a.W;
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < W; ++q) s_l[q] = gld(a.gloss + (long)q * a.gstride);
+    cgl_weights(a.mode, W, gld(a.lam), a.beta, s_l, s_al, s_t[0], s_t[1]);
+    if (blockIdx.x == 0)
+      for (int q = 0; q < W; ++q) { gst(a.alpha_all + q, s_al[q]); gst(a.losses_all + q, s_l[q]); }
+  }
+  __syncthreads();
+  gcf4p d4 = (gcf4p)a.d;
+  gf4p o4 = (gf4p)a.out;
+  const float a0 = s_al[0];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.nx4; i += (long)gridDim.x * 256) {
+    const f32x4 v = d4[i];
+    f32x4 acc;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = v[c] * a0;
+    // plain operators under this function's contract(off): the __fmul_rn / __fadd_rn wrappers are inlined with their
+    // own contraction setting, and a multiply and an add that both allow it are fused after inlining
+    for (int q = 1; q < W; ++q) {
+      const f32x4 u = d4[q * a.nx4 + i];
+      const float al = s_al[q];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float p = u[c] * al;
+        acc[c] = acc[c] + p;
+      }
+    }
+    o4[i] = acc;
+  }
+}
+
+__global__ __launch_bounds__(256) void cgl_conv_round_log_group_k(cgl_conv_round_log_args a, int W) {
+  int rnd = a.round, gs = a.g_step, ds = a.d_step;
+  if (a.counters) { rnd = gldi(a.counters) + 1; gs = gldi(a.counters + 1) + 1; ds = gldi(a.counters + 2) + 1; }
+  float lam_new = 0.f;
+  const unsigned w = cgl_conv_log_group_word(a, W, rnd, gs, ds, (int)threadIdx.x, lam_new);
+  __syncthreads();                   // (every worker's lanes have read Lambda before worker 0 advances it)
+  cgl_conv_log_group_store(a, W, rnd, (int)threadIdx.x, w, lam_new);
 }
 
 // Real-batch gather of the worker's sampler: dst[r] = src[idx ? idx[r] : row0 + r] (rows of
@@ -2591,13 +2796,17 @@ int cgl_conv_wgrad_defer_end(void* stream) {
   }
   const int blocks = m.begin[m.n] + m.c1_blocks + m.fbeg[m.nfin] + m.d1_blocks + ((m.cnt || m.lg.ring) ? 1 : 0);
   if (blocks == 0) return CGL_OK;
-  hipLaunchKernelGGL(cgl_conv_wgrad_reduce_multi, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
+  if (m.lg.ring && m.lg_group > 1)
+    hipLaunchKernelGGL(cgl_conv_wgrad_reduce_multi_grp, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
+  else
+    hipLaunchKernelGGL(cgl_conv_wgrad_reduce_multi, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
   return (int)hipGetLastError();
 }
 
 // Launch batching (cgl_conv_batch_begin / _end): between the two calls, cgl_conv_pack_multi,
 // cgl_dropout2d_masks(_dev), cgl_normal_fill_dev, cgl_sample_rows_dev and cgl_adv_loss (two at most) record their
-// (validated) arguments instead of launching (one of each at most); _end launches them as one cgl_conv_begin_k.
+// (validated) arguments instead of launching (one of each at most); _end launches them as one cgl_conv_begin_k --
+// or, with a grouped cgl_dropout2d_masks_dev_multi / cgl_sample_rows_dev_multi recorded, cgl_conv_begin_multi_k.
 // Every other launching entry point of the library returns CGL_E_STATE while a batch is open on the calling
 // thread (CGL_BATCH_GUARD), so nothing can be launched ahead of the deferred calls on the stream.
 namespace {
@@ -2605,6 +2814,10 @@ struct ConvBatch {
   bool on = false;
   hipStream_t s = nullptr;
   CglConvBeginArgs a{};
+  // grouped jobs of the co-located round start (cgl_dropout2d_masks_dev_multi, cgl_sample_rows_dev_multi): with
+  // either recorded, _end launches cgl_conv_begin_multi_k
+  const CglMasksTab* mm_tab = nullptr; const int* mm_round = nullptr; unsigned long long mm_stride = 0; int mmb = 0;
+  const CglSampleTab* sm_tab = nullptr; const int* sm_round = nullptr; int smb = 0;
 };
 thread_local ConvBatch t_batch;
 }  // namespace
@@ -2618,7 +2831,15 @@ int cgl_conv_batch_begin(void* stream) {
   t_batch.on = true;
   t_batch.s = (hipStream_t)stream;
   std::memset(&t_batch.a, 0, sizeof(t_batch.a));
+  t_batch.mm_tab = nullptr; t_batch.mmb = 0;
+  t_batch.sm_tab = nullptr; t_batch.smb = 0;
   return 0;
+}
+
+int cgl_conv_batch_cancel(void) {
+  if (!t_batch.on) return CGL_E_STATE;
+  t_batch.on = false;
+  return CGL_OK;
 }
 
 int cgl_conv_batch_end(void* stream) {
@@ -2626,6 +2847,15 @@ int cgl_conv_batch_end(void* stream) {
   t_batch.on = false;
   const CglConvBeginArgs& a = t_batch.a;
   const int blk = a.pb + a.mb + a.nb + a.sb + a.lb;
+  if (t_batch.mmb || t_batch.smb) {
+    CglConvBeginMultiArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.base = a;
+    m.mm_tab = t_batch.mm_tab; m.mm_round = t_batch.mm_round; m.mm_stride = t_batch.mm_stride; m.mmb = t_batch.mmb;
+    m.sm_tab = t_batch.sm_tab; m.sm_round = t_batch.sm_round; m.smb = t_batch.smb;
+    hipLaunchKernelGGL(cgl_conv_begin_multi_k, dim3(blk + m.mmb + m.smb), dim3(256), 0, (hipStream_t)stream, m);
+    return (int)hipGetLastError();
+  }
   if (blk == 0) return 0;
   hipLaunchKernelGGL(cgl_conv_begin_k, dim3(blk), dim3(256), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
@@ -3044,6 +3274,151 @@ int cgl_counters_add(int* p, int n, int v, void* stream) {
   CGL_BATCH_GUARD();
   if (!p || n < 1 || n > 64) return CGL_E_ARG;
   hipLaunchKernelGGL(cgl_counters_add_k, dim3(1), dim3(64), 0, (hipStream_t)stream, p, n, v);
+  return (int)hipGetLastError();
+}
+
+// ---- co-located conv workers: grouped state ops, the exchange, the grouped round log ----
+// a job table goes to the device as cgl_linear_prepare's descriptor does: the buffer may have been allocated /
+// zeroed on a non-blocking stream that the null stream's copy does not wait for, so the device is drained first
+static int tab_upload(void* desc_dev, const void* host, size_t bytes) {
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(desc_dev, host, bytes, hipMemcpyHostToDevice);
+  return (int)e;
+}
+
+int64_t cgl_sample_rows_dev_multi_desc_bytes(int njobs) {
+  if (njobs < 1 || njobs > CGL_MAX_COLOCATED) return CGL_E_ARG;
+  return (int64_t)sizeof(CglSampleTab);
+}
+
+int cgl_sample_rows_dev_multi_prepare(int njobs, const cgl_sample_job* jobs, int nrows, int row_floats,
+                                      void* desc_dev, int* blocks_out) {
+  CGL_BATCH_GUARD();
+  if (njobs < 1 || njobs > CGL_MAX_COLOCATED || !jobs || !desc_dev || !al16(desc_dev) || !blocks_out || nrows < 1 ||
+      (int64_t)njobs * nrows > (1 << 24) || row_floats < 4 || row_floats % 4)
+    return CGL_E_ARG;
+  CglSampleTab t;
+  std::memset(&t, 0, sizeof(t));
+  t.njobs = njobs; t.nrows = nrows; t.rowf = row_floats;
+  for (int q = 0; q < njobs; ++q) {
+    const cgl_sample_job& J = jobs[q];
+    if (!J.src || !J.dst || J.n_src < 1 || (!J.nv_out && J.n_src < nrows) || !al16(J.src) || !al16(J.dst))
+      return CGL_E_ARG;
+    t.j[q] = J;
+  }
+  *blocks_out = njobs * nrows;      // one workgroup per (job, row)
+  return tab_upload(desc_dev, &t, sizeof(t));
+}
+
+int cgl_sample_rows_dev_multi(const void* desc_dev, int blocks, const int* round_dev, void* stream) {
+  if (!desc_dev || !al16(desc_dev) || !round_dev || blocks < 1 || blocks > (1 << 24)) return CGL_E_ARG;
+  if (t_batch.on) {
+    if (t_batch.smb || (hipStream_t)stream != t_batch.s) return CGL_E_ARG;
+    t_batch.sm_tab = (const CglSampleTab*)desc_dev; t_batch.sm_round = round_dev; t_batch.smb = blocks;
+    return 0;
+  }
+  hipLaunchKernelGGL(cgl_sample_rows_multi_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                     (const CglSampleTab*)desc_dev, round_dev);
+  return (int)hipGetLastError();
+}
+
+int64_t cgl_dropout2d_masks_dev_multi_desc_bytes(int nm) {
+  if (nm < 1 || nm > CGL_MASKS_MULTI_MAX) return CGL_E_ARG;
+  return (int64_t)sizeof(CglMasksTab);
+}
+
+int cgl_dropout2d_masks_dev_multi_prepare(int nm, const cgl_mask_job* jobs, double p, void* desc_dev,
+                                          int* blocks_out) {
+  CGL_BATCH_GUARD();
+  if (nm < 1 || nm > CGL_MASKS_MULTI_MAX || !jobs || !desc_dev || !al16(desc_dev) || !blocks_out ||
+      !(p >= 0.0 && p < 1.0))
+    return CGL_E_ARG;
+  CglMasksTab t;
+  std::memset(&t, 0, sizeof(t));
+  t.nm = nm;
+  t.keep = (float)(1.0 - p);          // as dropout2d_masks_impl
+  t.scale = 1.0f / t.keep;
+  int64_t blk = 0;
+  for (int j = 0; j < nm; ++j) {
+    const cgl_mask_job& J = jobs[j];
+    if (!J.mask || J.n < 1 || J.C < 1) return CGL_E_ARG;
+    t.j[j].mask = J.mask;
+    t.j[j].n = (long)J.n * J.C;
+    t.j[j].seed = J.seed;
+    t.j[j].ctr = J.counter;
+    t.j[j].blk_begin = (int)blk;
+    blk += (t.j[j].n + 255) / 256;
+    if (blk > (1 << 24)) return CGL_E_ARG;
+  }
+  t.blocks = (int)blk;
+  *blocks_out = (int)blk;
+  return tab_upload(desc_dev, &t, sizeof(t));
+}
+
+int cgl_dropout2d_masks_dev_multi(const void* desc_dev, int nm, int blocks, const int* round_dev,
+                                  unsigned long long round_stride, void* stream) {
+  if (!desc_dev || !al16(desc_dev) || !round_dev || nm < 1 || nm > CGL_MASKS_MULTI_MAX || blocks < nm ||
+      blocks > (1 << 24))
+    return CGL_E_ARG;
+  if (t_batch.on) {
+    if (t_batch.mmb || (hipStream_t)stream != t_batch.s) return CGL_E_ARG;
+    t_batch.mm_tab = (const CglMasksTab*)desc_dev; t_batch.mm_round = round_dev; t_batch.mm_stride = round_stride;
+    t_batch.mmb = blocks;
+    return 0;
+  }
+  hipLaunchKernelGGL(cgl_dropout_masks_multi_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                     (const CglMasksTab*)desc_dev, round_dev, round_stride);
+  return (int)hipGetLastError();
+}
+
+int cgl_bcast_rows(const float* src, int64_t n, float* dst0, int64_t dst_stride, int copies, void* stream) {
+  CGL_BATCH_GUARD();
+  if (!src || !dst0 || !al16(src) || !al16(dst0) || n < 4 || n % 4 || dst_stride < n || dst_stride % 4 ||
+      copies < 1 || copies > CGL_MAX_COLOCATED)
+    return CGL_E_ARG;
+  const int grid = (int)std::min<int64_t>((n / 4 + 255) / 256, 1024);
+  hipLaunchKernelGGL(cgl_bcast_rows_k, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (long)(n / 4), dst0,
+                     (long)(dst_stride / 4), copies);
+  return (int)hipGetLastError();
+}
+
+int cgl_conv_alpha_combine(int weighting, int workers, const float* beta_host, const float* gloss, int gloss_stride,
+                           const float* lam_dev, const float* d, int64_t nx, float* dimg, float* alpha_all,
+                           float* losses_all, void* stream) {
+  CGL_BATCH_GUARD();
+  if (weighting < 0 || weighting > 4 || workers < 2 || workers > CGL_MAX_COLOCATED || !beta_host || !gloss ||
+      gloss_stride < 1 || !lam_dev || !d || !dimg || !alpha_all || !losses_all || nx < 4 || nx % 4 || !al16(d) ||
+      !al16(dimg))
+    return CGL_E_ARG;
+  CglCombineArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.mode = weighting; a.W = workers; a.gstride = gloss_stride;
+  for (int q = 0; q < workers; ++q) a.beta[q] = beta_host[q];
+  a.gloss = gloss; a.lam = lam_dev; a.d = d; a.out = dimg; a.alpha_all = alpha_all; a.losses_all = losses_all;
+  a.nx4 = (long)(nx / 4);
+  const int grid = (int)std::min<int64_t>((nx / 4 + 255) / 256, 1024);
+  hipLaunchKernelGGL(cgl_conv_alpha_combine_k, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+static int conv_log_group_ok(const cgl_conv_round_log_args* a, int workers) {
+  if (const int rc = conv_log_args_ok(a)) return rc;
+  if (workers < 2 || workers > CGL_MAX_COLOCATED || a->n_workers != workers || a->rank != 0) return CGL_E_ARG;
+  return CGL_OK;
+}
+
+int cgl_conv_wgrad_defer_log_group(const cgl_conv_round_log_args* a, int workers) {
+  if (!t_wdefer.on || t_wdefer.m.lg.ring) return CGL_E_STATE;
+  if (const int rc = conv_log_group_ok(a, workers)) return rc;
+  t_wdefer.m.lg = *a;
+  t_wdefer.m.lg_group = workers;
+  return CGL_OK;
+}
+
+int cgl_conv_round_log_group(const cgl_conv_round_log_args* a, int workers, void* stream) {
+  CGL_BATCH_GUARD();
+  if (const int rc = conv_log_group_ok(a, workers)) return rc;
+  hipLaunchKernelGGL(cgl_conv_round_log_group_k, dim3(1), dim3(256), 0, (hipStream_t)stream, *a, workers);
   return (int)hipGetLastError();
 }
 

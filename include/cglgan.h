@@ -455,6 +455,9 @@ int cgl_conv_pack_multi(int njobs, const CglConvPackJob* jobs, void* stream);
  * returns CGL_E_STATE without launching, so nothing can run ahead of the deferred calls. */
 int cgl_conv_batch_begin(void* stream);
 int cgl_conv_batch_end(void* stream);
+/* Close an open batch WITHOUT launching what it recorded (an error path, or a caller that only probed the recording
+ * rules).  CGL_E_STATE when no batch is open. */
+int cgl_conv_batch_cancel(void);
 /* Deferred weight-gradient reductions (the conv round's D and G backward): between cgl_conv_wgrad_defer_begin()
  * and cgl_conv_wgrad_defer_end(stream), these calls on the calling thread record their last step instead of
  * launching it: cgl_conv3x3_bwd_weight(_bnin / _actdrop) launch their MFMA kernel and record the fixed-order split
@@ -815,6 +818,64 @@ int cgl_sample_rows_dev(const float* src, int n_src, int nrows, int row_floats, 
                         const int* round_dev, float* dst, int* nv_out, void* stream);
 /* p[i] += v for i < n (<= 64): advances the device round state */
 int cgl_counters_add(int* p, int n, int v, void* stream);
+
+/* ---- co-located conv workers (ConvGanStep(colocated=W)): grouped state ops and the exchange ---
+ * One context runs a server's W = 2 .. CGL_MAX_COLOCATED workers: one G, W discriminators.  The per-worker
+ * start-of-round ops below run as ONE launch over all workers; each is bitwise the W single calls it groups, and
+ * each is accepted inside cgl_conv_batch_begin / _end (one of each at most, beside the single forms' own slots).
+ * Their job tables (up to 128 masks) do not fit the batched launch's argument segment, so they live in device
+ * memory: _prepare validates the jobs and writes the table once -- a synchronous copy behind a device drain, as
+ * cgl_linear_prepare's descriptor -- and the launch takes the prepared table.  The kernels take jobs, rows
+ * and sizes from the table alone; _prepare returns the table's workgroup count, which every launch of it passes (a
+ * workgroup past the table's own count does nothing; a smaller count leaves the last jobs undone). */
+typedef struct cgl_sample_job {   /* one cgl_sample_rows_dev call of the group */
+  const float* src;               /* [n_src][row_floats] resident shard, 16-byte aligned                    */
+  float* dst;                     /* [nrows][row_floats], 16-byte aligned                                    */
+  int* nv_out;                    /* as cgl_sample_rows_dev (null: drop_last, needs n_src >= nrows)           */
+  unsigned long long seed;
+  int n_src, reserved_;
+} cgl_sample_job;
+int64_t cgl_sample_rows_dev_multi_desc_bytes(int njobs);
+/* *blocks_out: the launch's workgroups, one per (job, row) (pass it to every launch of this table) */
+int cgl_sample_rows_dev_multi_prepare(int njobs, const cgl_sample_job* jobs, int nrows, int row_floats,
+                                      void* desc_dev, int* blocks_out);
+/* round_dev as cgl_sample_rows_dev, shared by the jobs; the jobs, rows and row length are the table's */
+int cgl_sample_rows_dev_multi(const void* desc_dev, int blocks, const int* round_dev, void* stream);
+#define CGL_MASKS_MULTI_MAX 128   /* CGL_MAX_COLOCATED workers x 8 masks */
+typedef struct cgl_mask_job {     /* one mask of cgl_dropout2d_masks_dev, with a seed of its own */
+  float* mask;
+  int n, C;
+  unsigned long long seed, counter;
+} cgl_mask_job;
+int64_t cgl_dropout2d_masks_dev_multi_desc_bytes(int nm);
+/* *blocks_out: the launch's workgroups (pass it to every launch of this table) */
+int cgl_dropout2d_masks_dev_multi_prepare(int nm, const cgl_mask_job* jobs, double p, void* desc_dev,
+                                          int* blocks_out);
+/* The per-mask-seed form of cgl_dropout2d_masks_dev: mask j from jobs[j].seed with counter jobs[j].counter +
+ * round_stride * (*round_dev). */
+int cgl_dropout2d_masks_dev_multi(const void* desc_dev, int nm, int blocks, const int* round_dev,
+                                  unsigned long long round_stride, void* stream);
+/* dst0[q * dst_stride + i] = src[i] for q < copies, i < n (the shared fake batch Xd behind every worker's real
+ * rows).  n % 4 == 0, dst_stride % 4 == 0, 16-byte aligned pointers; copies 1 .. CGL_MAX_COLOCATED. */
+int cgl_bcast_rows(const float* src, int64_t n, float* dst0, int64_t dst_stride, int copies, void* stream);
+/* The co-located exchange in one launch: alpha = weights(weighting, *lam_dev, beta, l) of the W G losses
+ * l_q = gloss[q * gloss_stride] (cgl_weights, as cgl_weights_scale), alpha_all[W] and losses_all[W] written, and
+ * dimg[i] = ((alpha_0 d[0][i]) + alpha_1 d[1][i]) + ... + alpha_{W-1} d[W-1][i] over d [W][nx]: every product
+ * rounded to fp32 before its add, no contraction, worker order -- bitwise W cgl_weights_scale calls followed by the
+ * rank-order sum of their buffers.  lam_dev is the device Lambda the round log advances, so the launch can sit
+ * inside a multi-round graph.  dimg may be d[0].  16-byte loads and stores: nx % 4 == 0, d and dimg 16-byte
+ * aligned.  CGL_E_ARG: a null pointer, misalignment, nx < 4 or nx % 4, workers outside 2 .. CGL_MAX_COLOCATED,
+ * gloss_stride < 1, a weighting outside CGL_WEIGHT_*. */
+int cgl_conv_alpha_combine(int weighting, int workers, const float* beta_host, const float* gloss, int gloss_stride,
+                           const float* lam_dev, const float* d, int64_t nx, float* dimg, float* alpha_all,
+                           float* losses_all, void* stream);
+/* The grouped forms of cgl_conv_wgrad_defer_log / cgl_conv_round_log: `workers` records per round, one ring per
+ * worker.  a->ring is [workers][CGL_CONV_ROUND_LOG_CAP], a->lbuf [workers][8] (d_real, d_fake, g_loss of worker q at
+ * 8 q), a->nv [workers]; a->n_workers == workers (2 .. CGL_MAX_COLOCATED), a->rank == 0, losses_all and alpha_all
+ * given.  Record q is the record cgl_conv_round_log writes with rank = q on worker q's words; the device Lambda
+ * advances once.  Call-order rules and counters as the single forms (the two forms share the deferral's one slot). */
+int cgl_conv_wgrad_defer_log_group(const cgl_conv_round_log_args* a, int workers);
+int cgl_conv_round_log_group(const cgl_conv_round_log_args* a, int workers, void* stream);
 
 /* ---- evaluation ------------------------------------------------------------------------------
  * KL score of generated 2-D samples (CGLGAN/2DMG/main.py:63-101 plot_2d): np.histogram2d of the
